@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- STFT frames/s of the phase-vocoder analysis stage (PV.run_pv) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c4]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, ramps the clocks, runs the W warm-up steps, times the K steps and prints one JSON line (`value`,
+`ms_per_step` = wall milliseconds of one timed step, ...).  --dump-outputs DIR: the arrays the last timed step computed
+(f, mag, ph, realph, binno as [frames, npks], totalmag and t as [frames]; float64) as DIR/<name>.npy, a seeded sample of
+frames when they exceed DUMP_MAX_BYTES.  --full: everything else below (checks, baselines, other sizes and precisions).
 
 N > 1 without a torch.distributed environment: bench.py launches itself as N ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py ...`, as a child process, before anything
@@ -17,7 +22,7 @@ A "step" is one full run_pv pass over the workload, with the signal(s) already r
   it overlaps the next step's kernels; all gathers have completed and been unpacked before the clock stops).
 value = frames processed by all ranks / wall time of the K timed steps (max over ranks).
 
-Also on the same JSON line (rank 0):
+With --full, also on the same JSON line (rank 0):
   roofline     -- the dominant kernel.  bound "hbm": achieved = ITS algorithmic bytes per launch (DESIGN.md 3:
                   the fused kernels read hop*4 B and write (5*npks+2)*8 B per frame; the three-kernel path's
                   kernels have their own figures) / its mean launch duration, measured with HIP events that
@@ -305,6 +310,28 @@ def compact_line(full, detail_path):
     return s
 
 
+DUMP_MAX_BYTES = 60 * 2 ** 20       # --dump-outputs: array bytes in all (the .npy headers stay well inside 64 MB)
+DETAIL_DEFAULT = os.path.join("bench_out", "bench_detail.json")     # --full's record, relative to the repository root
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Writes `arrays` (name -> float64 array, all with the frame axis first) as out_dir/<name>.npy.  When they exceed
+    `max_bytes`, the same seeded, sorted sample of frames is taken from every array and its frame numbers are written as
+    frame_index.npy (float64), so that two builds dump the same rows.  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    nf = len(next(iter(arrays.values())))
+    per_frame = sum(v.nbytes for v in arrays.values()) // max(nf, 1)
+    if per_frame * nf > max_bytes:
+        keep = max_bytes // (per_frame + 8)                           # (+ 8 B per frame: frame_index itself)
+        idx = np.sort(np.random.default_rng(0).choice(nf, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["frame_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,8 +350,14 @@ def main():
     ap.add_argument("--streams", type=int, default=1, choices=(1, 2),
                     help="2: consecutive steps alternate between two streams (hides the launch gap and the kernel tail; "
                          "per-kernel durations then overlap and no longer compare with rocprofv3's)")
-    ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="where the full record goes (config5 points, workloads, other_nfft, issue view, every oracle check); stdout carries one compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the run from idle, per-kernel timings and roofline, the oracle checks, the CPU baseline, "
+                         "float64, other material and sizes, config 5, the host batch entry and the gathered-block checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float64; a seeded sample of frames beyond %d MB)" % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument("--detail", default=None,
+                    help="where the full record goes (config5 points, workloads, other_nfft, issue view, every oracle check); stdout carries one compact line "
+                         "(default: none for a plain run, %s with --full)" % DETAIL_DEFAULT)
     ap.add_argument("--seconds", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--shard-signals", type=int, default=0, help=argparse.SUPPRESS)    # tests: fewer signals per GPU than the workload's
     ap.add_argument("--comm-cus", type=int, default=0, help="gathered runs: compute units left without an analysis workgroup, for the collective's kernels (0: none)")
@@ -333,6 +366,10 @@ def main():
                     help="with a gather (N > 1, or PVX_BENCH_FORCE_GATHER=1): compare the gathered + unpacked results of rank 0's first "
                          "that many signals with the oracle (non-zero exit code on a miss)")
     args = ap.parse_args()
+    if args.check_gathered and not args.full:
+        ap.error("--check-gathered is one of the --full checks")
+    if args.full and args.detail is None:
+        args.detail = DETAIL_DEFAULT
 
     # PVX_BENCH_SELF_LAUNCH=1: take the launcher path even for one rank (tests: what `--gpus 8` does on an 8-GPU node)
     if (args.gpus > 1 or os.environ.get("PVX_BENCH_SELF_LAUNCH") == "1") and "WORLD_SIZE" not in os.environ:
@@ -511,9 +548,9 @@ def main():
 
     # ---- from idle first: the W warm-up steps and the K timed steps exactly as the contract says, on a card that has
     # just been handed the workload (a step is 0.14 ms: W + K steps are 3 ms of work and the card needs tens of
-    # milliseconds of continuous work to leave its idle clocks) -> `value_from_idle`
+    # milliseconds of continuous work to leave its idle clocks) -> `value_from_idle` (--full)
     idle = None
-    if args.clock_warmup_ms > 0:
+    if args.clock_warmup_ms > 0 and args.full:
         for _ in range(args.warmup):
             step()
         idle = timed(args.steps)
@@ -543,22 +580,31 @@ def main():
     if os.environ.get("PVX_BENCH_NO_SUBMIT"):                     # (A/B only: no collective was posted, nothing below applies)
         print(json.dumps(dict(ab="gathered step without its collective", ms_per_step=round(elapsed_local / args.steps * 1e3, 4), host_issue_ms_per_step=round(host_issue_ms, 4))))
         return 0
-    if gathered:
+    if gathered and (args.full or args.dump_outputs):
         local_block(counter[0] - 1, last)         # what was timed is what is checked: the last timed step's rows, from the block it sent
     res = res2[last]
-    # ---- the same K steps once more with libpvx_hip's stage events on the launch stream: per-kernel
-    # launch durations for the roofline line (kept out of the timed region: the extra event records
-    # cost a few percent)
-    _lib.check(lib.pvx_plan_set_timing(plan, 1), "pvx_plan_set_timing")
-    for _ in range(args.steps):
-        last2 = step(single=True)                 # one stream, one plan: launches do not overlap here
-    fence()
-    if gathered:
-        local_block(counter[0] - 1, last2)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result block (this rank's rows), before anything else runs on these buffers
+        h = res.cpu().numpy()
+        nk = FT * K
+        outs = {k: h[i * nk:(i + 1) * nk].reshape(FT, K) for i, k in enumerate(("f", "mag", "ph", "realph", "binno"))}
+        outs.update(totalmag=h[5 * nk: 5 * nk + FT], t=h[nres - FT:])
+        dump_outputs(args.dump_outputs, outs)
     ms = (ctypes.c_double * 4)()
     nl = (ctypes.c_int64 * 4)()
-    _lib.check(lib.pvx_plan_get_timing(plan, ms, nl), "pvx_plan_get_timing")
-    _lib.check(lib.pvx_plan_set_timing(plan, 0), "pvx_plan_set_timing")
+    last2 = last
+    if args.full:
+        # ---- the same K steps once more with libpvx_hip's stage events on the launch stream: per-kernel
+        # launch durations for the roofline line (kept out of the timed region: the extra event records
+        # cost a few percent)
+        _lib.check(lib.pvx_plan_set_timing(plan, 1), "pvx_plan_set_timing")
+        for _ in range(args.steps):
+            last2 = step(single=True)                 # one stream, one plan: launches do not overlap here
+        fence()
+        if gathered:
+            local_block(counter[0] - 1, last2)
+        _lib.check(lib.pvx_plan_get_timing(plan, ms, nl), "pvx_plan_get_timing")
+        _lib.check(lib.pvx_plan_set_timing(plan, 0), "pvx_plan_set_timing")
     fft_mode = int(lib.pvx_plan_get_fft_mode(plan))
     elapsed = elapsed_local
     elapsed_idle = idle[0] if idle else None
@@ -575,6 +621,13 @@ def main():
     gather_info = None
     gather_check_failed = False
     if gathered and rank == 0:
+        gather_info = dict(collective="one asynchronous RCCL gather per step to rank 0, double-buffered",
+                           unpack=("inside the step, on a side stream of rank 0" if args.unpack_in_step else
+                                   "on demand: the gathered blocks stay in the wire format on rank 0 (decoded after the timed region for the checks)"),
+                           wire_format=wire_format, wire_bytes_per_slot=(14 if wire_format == 2 else (18 if args.precision == 32 else 26)),
+                           rccl_world=int(dist.get_world_size()), wire_bytes_per_rank=int(wire.nbytes),
+                           result_bytes_per_rank=int(wire.result_numel() * 8))
+    if gathered and rank == 0 and args.full:
         # the block rank 0 received from itself must be, bit for bit, what its kernels wrote
         torch.cuda.synchronize(dev)
         if not args.unpack_in_step:
@@ -582,13 +635,7 @@ def main():
             torch.cuda.synchronize(dev)
         if not torch.equal(full[0].view(torch.int64), res2[last2][: wire.result_numel()].view(torch.int64)):
             sys.exit("bench.py: the gathered + unpacked block of rank 0 differs from its local result")
-        n_ok = int((full[:, : FT * K] > 0).sum().item())
-        gather_info = dict(collective="one asynchronous RCCL gather per step to rank 0, double-buffered",
-                           unpack=("inside the step, on a side stream of rank 0" if args.unpack_in_step else
-                                   "on demand: the gathered blocks stay in the wire format on rank 0 (decoded after the timed region for the checks)"),
-                           wire_format=wire_format, wire_bytes_per_slot=(14 if wire_format == 2 else (18 if args.precision == 32 else 26)),
-                           rccl_world=int(dist.get_world_size()), wire_bytes_per_rank=int(wire.nbytes),
-                           result_bytes_per_rank=int(wire.result_numel() * 8), valid_peaks_gathered=n_ok)
+        gather_info["valid_peaks_gathered"] = int((full[:, : FT * K] > 0).sum().item())
         if args.check_gathered > 0:
             # what arrived through pack -> RCCL gather -> unpack, against the oracle on the signals themselves
             from oracle import pvoracle
@@ -652,12 +699,15 @@ def main():
                                  "1.365e8 frames/s (60 % of 8 TB/s at the 35 168 B/frame of the three-kernel split)")
             if fft_mode in (1, 2, 3, 4, 5):
                 roofline["issue"] = issue_bound(dom["kernel"], fpl, dom["ms_per_launch"])
-        stage_s = sum(ms[i] for i in range(4)) * 1e-3 / args.steps
-        stage = dict(fft_mode=fft_mode, ms_per_step_kernels=round(stage_s * 1e3, 4),
-                     kernels=[{k: (round(v, 4) if isinstance(v, float) else v) for k, v in d.items()} for d in per],
-                     step_ms_hip_events=round(ev_ms / args.steps, 4))
+        step_ms_ev = round(ev_ms / args.steps, 4)
+        stage = None                                                # (per-kernel durations: --full only)
+        if args.full:
+            stage_s = sum(ms[i] for i in range(4)) * 1e-3 / args.steps
+            stage = dict(fft_mode=fft_mode, ms_per_step_kernels=round(stage_s * 1e3, 4),
+                         kernels=[{k: (round(v, 4) if isinstance(v, float) else v) for k, v in d.items()} for d in per],
+                         step_ms_hip_events=step_ms_ev)
 
-        extras_ok = world == 1 and args.workload == "c2" and not args.no_extras
+        extras_ok = args.full and world == 1 and args.workload == "c2" and not args.no_extras
         self_check = cpu = None
         checks_failed = []
 
@@ -702,7 +752,7 @@ def main():
             return d
 
         o = None
-        if world == 1 and args.workload == "c2" and not args.no_cpu_baseline:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_cpu_baseline:
             from oracle import pvoracle
             pvoracle.build()
             xs = x_host.astype(np.float64)
@@ -1080,8 +1130,8 @@ def main():
         if host_batch:
             line["host_batch"] = host_batch
         if gather_info:
-            gather_info["ms_per_step_kernels_only"] = stage["step_ms_hip_events"]
-            gather_info["exposed_ms_per_step"] = round(max(0.0, elapsed / args.steps * 1e3 - stage["step_ms_hip_events"]), 4)
+            gather_info["ms_per_step_kernels_only"] = step_ms_ev
+            gather_info["exposed_ms_per_step"] = round(max(0.0, elapsed / args.steps * 1e3 - step_ms_ev), 4)
             gather_info["host_issue_ms_per_step"] = round(host_issue_ms, 4)
             gather_info["note"] = ("exposed = wall time per step minus the analysis kernels' time on the compute stream (launch gaps included); "
                                    "host_issue = the host's time to issue a step (analysis launch + the collective's enqueue): a step cannot be shorter")
@@ -1093,15 +1143,17 @@ def main():
         if extras_ok:
             line["extras_ok"] = not checks_failed
         # the whole record goes to a file (and, pretty-printed, nowhere else); stdout gets ONE compact line the driver can parse
-        detail_path = args.detail if os.path.isabs(args.detail) else os.path.join(ROOT, args.detail)
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
-            with open(detail_path, "w") as fh:
-                json.dump(line, fh, indent=1)
-                fh.write("\n")
-        except OSError as e:
-            sys.stderr.write("bench.py: could not write %s: %s\n" % (detail_path, e))
-            detail_path = None
+        detail_path = None
+        if args.detail:
+            detail_path = args.detail if os.path.isabs(args.detail) else os.path.join(ROOT, args.detail)
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
+                with open(detail_path, "w") as fh:
+                    json.dump(line, fh, indent=1)
+                    fh.write("\n")
+            except OSError as e:
+                sys.stderr.write("bench.py: could not write %s: %s\n" % (detail_path, e))
+                detail_path = None
         print(compact_line(line, os.path.relpath(detail_path, ROOT) if detail_path else None))
         sys.stdout.flush()
         if rc:

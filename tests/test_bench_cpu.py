@@ -71,3 +71,22 @@ def test_the_stdout_line_of_a_multi_rank_run_and_of_a_bare_run():
     full = _full()
     full["config5"]["points"][3]["self_check"]["ok"] = False
     assert json.loads(bench.compact_line(full, "d.json"))["c5_all_ok"] is False
+
+
+def test_dump_outputs_writes_float64_and_samples_the_same_frames_beyond_the_cap(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    arrays = dict(f=rng.standard_normal((1000, 8)), binno=rng.integers(0, 1025, (1000, 8)), t=np.arange(1000) * 512.0)
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["binno", "f", "t"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    # over the cap: one seeded, sorted sample of frames, the same rows of every array, and their frame numbers
+    cap = 20000
+    names = bench.dump_outputs(str(tmp_path / "a"), arrays, max_bytes=cap)
+    assert names == ["binno", "f", "frame_index", "t"] and bench.dump_outputs(str(tmp_path / "b"), arrays, max_bytes=cap) == names
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    idx = got["frame_index"].astype(np.int64)
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0) and sum(v.nbytes for v in got.values()) <= cap
+    assert np.array_equal(got["f"], arrays["f"][idx]) and np.array_equal(got["t"], arrays["t"][idx])
+    assert all(np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), got[k]) for k in names)

@@ -29,8 +29,8 @@ def _detail(j):
         return json.load(fh)
 
 
-def test_bench_line_and_self_check():
-    rc, j, err = _run(["--steps", "3", "--warmup", "1", "--seconds", "20", "--no-extras", "--detail", "gpurun_out/test_bench_detail_a.json"])
+def test_bench_line_and_self_check(tmp_path):
+    rc, j, err = _run(["--full", "--steps", "3", "--warmup", "1", "--seconds", "20", "--no-extras", "--detail", str(tmp_path / "detail.json")])
     assert rc == 0 and j is not None, err[-2000:]
     for k in ("metric", "value", "value_from_idle", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "self_check"):
@@ -52,10 +52,10 @@ def test_bench_line_and_self_check():
         assert 0.0 < d["roofline"]["issue"]["valu_issue"]["frac"] <= 1.0
 
 
-def test_bench_extras_are_all_checked_against_the_oracle():
-    """The default line's extra objects on a short signal: float64, the other material, nfft 4096 / 8192, and the rest of
+def test_bench_extras_are_all_checked_against_the_oracle(tmp_path):
+    """The --full line's extra objects on a short signal: float64, the other material, nfft 4096 / 8192, and the rest of
     the path (tracker + resynthesis on the headline results) -- every one of them carries an oracle check that passed."""
-    rc, jc, err = _run(["--steps", "3", "--warmup", "1", "--seconds", "30", "--c5-seconds", "20", "--detail", "gpurun_out/test_bench_detail_b.json"])
+    rc, jc, err = _run(["--full", "--steps", "3", "--warmup", "1", "--seconds", "30", "--c5-seconds", "20", "--detail", str(tmp_path / "detail.json")])
     assert rc == 0 and jc is not None, err[-2000:]
     assert jc["extras_ok"] and jc["c5_all_ok"] and jc["f64_ok"] and jc["f64_value"] > 0 and jc["chain_total_ms"] > 0 and jc["c5_min_vs_target"] > 0
     j = _detail(jc)
@@ -85,7 +85,7 @@ def test_bench_extras_are_all_checked_against_the_oracle():
 
 
 def test_bench_forced_gather_exercises_rccl():
-    rc, j, err = _run(["--steps", "4", "--warmup", "1", "--seconds", "20", "--no-extras", "--no-cpu-baseline"],
+    rc, j, err = _run(["--full", "--steps", "4", "--warmup", "1", "--seconds", "20", "--no-extras", "--no-cpu-baseline"],
                       env={"PVX_BENCH_FORCE_GATHER": "1", "MASTER_PORT": "29641"})
     assert rc == 0 and j is not None, err[-2000:]
     g = j["gather"]
@@ -100,7 +100,7 @@ def test_bench_self_launch_c4_gather_matches_oracle():
     env = {"PVX_BENCH_SELF_LAUNCH": "1", "PVX_BENCH_FORCE_GATHER": "1"}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         os.environ.pop(k, None)
-    rc, j, err = _run(["--gpus", "1", "--workload", "c4", "--shard-signals", "3", "--seconds", "5", "--steps", "3", "--warmup", "1",
+    rc, j, err = _run(["--full", "--gpus", "1", "--workload", "c4", "--shard-signals", "3", "--seconds", "5", "--steps", "3", "--warmup", "1",
                        "--check-gathered", "3"], env=env)
     assert rc == 0 and j is not None, err[-3000:]
     g = j["gather"]
@@ -119,3 +119,34 @@ def test_bench_refuses_more_ranks_than_gpus():
     n = torch.cuda.device_count()
     rc, j, err = _run(["--gpus", str(n + 1), "--steps", "1", "--warmup", "0"], timeout=120)
     assert rc != 0 and j is None and "GPU" in err
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_output(tmp_path):
+    """A plain run: the headline alone (no checks, baselines or extras) and, with --dump-outputs, the arrays of its last timed
+    step -- the oracle's result on the same seeded signal, and bit for bit what a --full run of the same arguments dumps."""
+    import numpy as np
+
+    import bench
+    from oracle import pvoracle
+    from tests.parity import compare_analysis
+    args = ["--steps", "5", "--warmup", "2", "--seconds", "20"]
+    rc, j, err = _run(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert rc == 0 and j is not None, err[-2000:]
+    assert j["steps"] == 5 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["unit"] == "frames/s" and j["dtype"] == "f32"
+    F = j["config"]["frames_per_gpu"]
+    assert abs(F / j["value"] * 1e3 - j["ms_per_step"]) <= 0.6e-4                   # (ms_per_step is rounded to 0.1 us)
+    assert all(j[k] is None for k in ("value_from_idle", "roofline", "cpu_baseline", "self_check", "detail")), j
+    names = ("f", "mag", "ph", "realph", "binno", "totalmag", "t")
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(tmp_path / "plain" / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float64 and len(v) == F for v in got.values())
+    assert all(got[n].shape == (F, 8) for n in names[:5]) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    o = pvoracle.analyze(bench.c2_signal(20).astype(np.float64), 44100, 2048, 512, 8)
+    assert np.array_equal(got["t"], o["t"])
+    c = compare_analysis(got, o, 2048, 512, 44100)
+    assert c["bad_peaks"] <= 1e-3 * max(c["ref_peaks"], 1) and c["f_norm"] <= 2e-5 and c["mag_norm"] <= 1e-6 and c["ph_norm"] <= 2e-6, c
+    rc, jf, err = _run(args + ["--full", "--no-extras", "--no-cpu-baseline", "--detail", str(tmp_path / "d.json"),
+                               "--dump-outputs", str(tmp_path / "full")])
+    assert rc == 0 and jf is not None and jf["roofline"] is not None, err[-2000:]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "full" / (n + ".npy")), got[n]), n

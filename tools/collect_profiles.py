@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Copy what tools/gpu_bench_round.sh left under gpurun_out/ into profiles/ (the tracked evidence bench.py and DESIGN.md
-cite):   python tools/collect_profiles.py r03
+"""Copy what tools/gpu_bench_round.sh left in its output folder into profiles/ (the tracked evidence bench.py and DESIGN.md
+cite):   python tools/collect_profiles.py r03 [OUTDIR]      (OUTDIR: the folder gpu_bench_round.sh wrote, default prof_out)
   profiles/sq_latest.json            SQ counters of every analysis / tracker / resynthesis kernel profiled this round, per-launch
                                      means (tools/prof_sq.sh), stamped with the fingerprint of the kernel sources (bench.py quotes
                                      it only when that matches the build it times); the same as profiles/<tag>_sq.json
@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 from bench import csrc_sha16  # noqa: E402
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.join(ROOT, "prof_out")
 P = os.path.join(ROOT, "profiles")
 FRAMES = 51676
 SHA = csrc_sha16()
@@ -32,7 +32,7 @@ def short_name(k):
     return m.group(1) if m else k
 
 
-# ---- SQ counters: every summary.json under gpurun_out/sq_<tag>*/
+# ---- SQ counters: every summary.json under OUTDIR/sq_<tag>*/
 sq = {"_csrc_sha16": SHA, "_tag": tag, "_frames_per_launch": FRAMES,
       "_method": ("rocprofv3 --pmc <8 SQ counters per pass> -- python3 tools/run_mode.py -1 harmonic 8 4 [precision] | tools/synth_time.py "
                   "(tools/prof_sq.sh): BASELINE config 2 signal, plan default fft mode; values are means over the kernel's launches; "
