@@ -373,6 +373,32 @@ int64_t pvx_funcwind(const double* x, int x_complex, int64_t n, const double* wi
 int64_t pvx_funcwind_dev(const double* d_x, int x_complex, int64_t n, const double* wind, int wlen, int hop,
                          int func, double divisor, double* d_out, void* stream);
 
+/* ---- time-domain periodicity: PeriodSeries (pypevoc/Periodicity.py:251-503) ----------------
+ *
+ * pvx_periodicity: Periodicity._calc + sort_strength (Periodicity.py:98-236) for the frames centred at
+ * idx[0..nidx) (host array; each frame x[idx - nwind/2 : idx + nwind - nwind/2] must lie inside x, else
+ * PVX_ERR_INVALID).  method: PVX_PERIOD_XCORR / PVX_PERIOD_AMDF; cand_method: PVX_CAND_*; threshold is
+ * PeakFinder's minval (0: min of the similarity slice), vthresh the voicing threshold.  Per frame i:
+ * ncands[i] <= ncand candidates sorted by decreasing strength in cand_period / cand_strength[i*ncand ..]
+ * (NaN beyond the count) and preferred[i] (-1 when there is none: the reference's `preferred = []`).
+ * 1 <= ncand <= 64; nwind <= 32768, else PVX_ERR_UNSUPPORTED.  float64 throughout, no host compute.
+ * pvx_periodicity_dev: x and the four outputs are device memory (idx and wind stay host arrays), work on
+ * `stream`, synchronised before the return.  Both return nidx or a negative status.  Calls share a per-device
+ * workspace kept for the process (grow-only buffers, one rocFFT plan per window length in use: memory does not grow
+ * with the number or length of signals) and take turns on it.
+ */
+typedef enum { PVX_PERIOD_XCORR = 0, PVX_PERIOD_AMDF = 1 } pvx_period_method;
+typedef enum { PVX_CAND_FFT = 0, PVX_CAND_MIN = 1, PVX_CAND_SIMILAR = 2, PVX_CAND_OTHER = 3 } pvx_cand_method;
+int64_t pvx_periodicity(const double* x, int64_t nsamp, const double* wind, int nwind, const int64_t* idx,
+                        int64_t nidx, int method, int cand_method, int mindelay, int maxdelay, double threshold,
+                        double vthresh, int ncand, double fftthresh, double* cand_period,
+                        double* cand_strength, int32_t* ncands, int32_t* preferred);
+int64_t pvx_periodicity_dev(const double* d_x, int64_t nsamp, const double* wind, int nwind, const int64_t* idx,
+                            int64_t nidx, int method, int cand_method, int mindelay, int maxdelay,
+                            double threshold, double vthresh, int ncand, double fftthresh,
+                            double* d_cand_period, double* d_cand_strength, int32_t* d_ncands,
+                            int32_t* d_preferred, void* stream);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

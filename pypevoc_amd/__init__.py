@@ -10,6 +10,9 @@ ctypes; see include/pvx.h, DESIGN.md and INTEGRATION.md.
 from .PVAnalysis import PV, SinSum, RegPartial, PVHarmonic  # noqa: F401  (pypevoc/__init__.py:1 exports PV, SinSum)
 from .PeakFinder import PeakFinder  # noqa: F401
 from .batch import PVBatch, PVMany  # noqa: F401
+from .Periodicity import (PeriodSeries, PeriodTimeSeries, period_marks_corr,  # noqa: F401  (pypevoc/__init__.py:2)
+                          period_marks_peak, period_marks_amdf)
 from ._lib import PvxError  # noqa: F401
 
-__all__ = ["PV", "PVHarmonic", "SinSum", "RegPartial", "PeakFinder", "PVBatch", "PVMany", "PvxError"]
+__all__ = ["PV", "PVHarmonic", "SinSum", "RegPartial", "PeakFinder", "PVBatch", "PVMany", "PvxError",
+           "PeriodSeries", "PeriodTimeSeries", "period_marks_corr", "period_marks_peak", "period_marks_amdf"]

@@ -118,6 +118,12 @@ SIGNATURES = {
     "pvx_analyze_dev_wire": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_void_p, ctypes.c_void_p]),
     "pvx_unpack_rows_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 8),
+    "pvx_periodicity": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int, c_int64_p, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                         ctypes.c_double, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "pvx_periodicity_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int, c_int64_p, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 5),
 }
 
 

@@ -2158,6 +2158,85 @@ extern "C" int64_t pvx_funcwind(const double* x, int x_complex, int64_t n, const
     return nfr;
 }
 
+// ---- time-domain periodicity (k_period.hip) ---------------------------------------------------
+// numpy's clipping of a slice bound on an array of `len` entries
+static int np_bound(int64_t b, int64_t len) {
+    if (b < 0) b += len;
+    return (int)(b < 0 ? 0 : (b > len ? len : b));
+}
+static int period_args(int64_t nsamp, const double* wind, int nwind, const int64_t* idx, int64_t nidx, int method, int cand_method,
+                       int mindelay, int maxdelay, int ncand, PeriodParams* p) {
+    if (nsamp < 0 || !wind || nwind < 1 || nidx < 0 || (nidx > 0 && !idx)) { pvx_set_error("bad periodicity argument"); return PVX_ERR_INVALID; }
+    if (method != PVX_PERIOD_XCORR && method != PVX_PERIOD_AMDF) { pvx_set_error("pvx_periodicity: unknown method %d", method); return PVX_ERR_INVALID; }
+    if (cand_method < PVX_CAND_FFT || cand_method > PVX_CAND_OTHER) { pvx_set_error("pvx_periodicity: unknown cand_method %d", cand_method); return PVX_ERR_INVALID; }
+    if (mindelay < 0) { pvx_set_error("pvx_periodicity: mindelay %d < 0", mindelay); return PVX_ERR_INVALID; }
+    if (ncand < 1 || ncand > PVX_PERIOD_MAX_NCAND) { pvx_set_error("pvx_periodicity: ncand %d outside 1..%d", ncand, PVX_PERIOD_MAX_NCAND); return PVX_ERR_UNSUPPORTED; }
+    if (nwind > PVX_PERIOD_MAX_NWIND) { pvx_set_error("pvx_periodicity: window of %d samples (the kernels take up to %d)", nwind, PVX_PERIOD_MAX_NWIND); return PVX_ERR_UNSUPPORTED; }
+    const int64_t n = nwind, nwl = n / 2;
+    for (int64_t i = 0; i < nidx; i++) {
+        if (idx[i] - nwl < 0 || idx[i] - nwl + n > nsamp) {
+            pvx_set_error("pvx_periodicity: the frame centred at %lld leaves the signal of %lld samples (window %d)", (long long)idx[i], (long long)nsamp, nwind);
+            return PVX_ERR_INVALID;
+        }
+    }
+    const int64_t len = method == PVX_PERIOD_AMDF ? n : 2 * n - 1;   // amdf(xw) has nwind entries, correlate(.., "full") 2*nwind-1
+    p->ns = np_bound(n - 1 - (int64_t)maxdelay, len);
+    p->ne = np_bound(n - 1 + (int64_t)maxdelay, len);
+    if (p->ns >= p->ne) { pvx_set_error("pvx_periodicity: maxdelay %d leaves the normalising slice empty (the reference raises ValueError)", maxdelay); return PVX_ERR_INVALID; }
+    const int pend = (int)std::min<int64_t>(std::max(maxdelay, 0), n);
+    if (method == PVX_PERIOD_AMDF) {
+        p->lo[0] = std::min(mindelay, pend); p->hi[0] = pend;
+        p->lo[1] = p->ns; p->hi[1] = p->ne;
+    } else {
+        const int64_t nmax = std::max(std::llabs((int64_t)p->ns - (n - 1)), std::llabs((int64_t)p->ne - 1 - (n - 1)));
+        p->lo[0] = 0; p->hi[0] = (int)std::min<int64_t>(n, std::max<int64_t>(pend, nmax + 1));
+        p->lo[1] = 0; p->hi[1] = 0;
+    }
+    p->nsamp = nsamp; p->nwind = nwind; p->nfr = nidx;
+    p->amdf = method == PVX_PERIOD_AMDF; p->cand_method = cand_method;
+    p->mindelay = mindelay; p->maxdelay = maxdelay; p->ncand = ncand;
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_periodicity_dev(const double* d_x, int64_t nsamp, const double* wind, int nwind, const int64_t* idx, int64_t nidx,
+                                       int method, int cand_method, int mindelay, int maxdelay, double threshold, double vthresh, int ncand,
+                                       double fftthresh, double* d_cand_period, double* d_cand_strength, int32_t* d_ncands,
+                                       int32_t* d_preferred, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    PeriodParams p = {};
+    if ((rc = period_args(nsamp, wind, nwind, idx, nidx, method, cand_method, mindelay, maxdelay, ncand, &p)) != PVX_OK) return rc;
+    if (nidx == 0) return 0;
+    if (!d_x || !d_cand_period || !d_cand_strength || !d_ncands || !d_preferred) { pvx_set_error("null periodicity array"); return PVX_ERR_INVALID; }
+    p.x = d_x;
+    p.threshold = threshold; p.vthresh = vthresh; p.fftthresh = fftthresh;
+    p.cand_period = d_cand_period; p.cand_strength = d_cand_strength; p.ncands = d_ncands; p.preferred = d_preferred;
+    if ((rc = pvx_period_run(p, wind, idx, (hipStream_t)stream)) != PVX_OK) return rc;   // synchronises the stream
+    return nidx;
+}
+
+extern "C" int64_t pvx_periodicity(const double* x, int64_t nsamp, const double* wind, int nwind, const int64_t* idx, int64_t nidx,
+                                   int method, int cand_method, int mindelay, int maxdelay, double threshold, double vthresh, int ncand,
+                                   double fftthresh, double* cand_period, double* cand_strength, int32_t* ncands, int32_t* preferred) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    PeriodParams chk = {};
+    if ((rc = period_args(nsamp, wind, nwind, idx, nidx, method, cand_method, mindelay, maxdelay, ncand, &chk)) != PVX_OK) return rc;
+    if (nidx == 0) return 0;
+    if (!x || !cand_period || !cand_strength || !ncands || !preferred) { pvx_set_error("null periodicity array"); return PVX_ERR_INVALID; }
+    const size_t cb = (size_t)nidx * ncand * 8, ib = (size_t)nidx * 4;
+    DevBuf dx, dp, ds, dn, dq;
+    if ((rc = dx.alloc((size_t)nsamp * 8)) != PVX_OK || (rc = dp.alloc(cb)) != PVX_OK || (rc = ds.alloc(cb)) != PVX_OK ||
+        (rc = dn.alloc(ib)) != PVX_OK || (rc = dq.alloc(ib)) != PVX_OK) return rc;
+    if ((rc = host_to_device(dx.p, x, (size_t)nsamp * 8)) != PVX_OK) return rc;
+    const int64_t r = pvx_periodicity_dev((const double*)dx.p, nsamp, wind, nwind, idx, nidx, method, cand_method, mindelay, maxdelay, threshold,
+                                          vthresh, ncand, fftthresh, (double*)dp.p, (double*)ds.p, (int32_t*)dn.p, (int32_t*)dq.p, nullptr);
+    if (r < 0) return r;
+    if ((rc = device_to_host(cand_period, dp.p, cb)) != PVX_OK || (rc = device_to_host(cand_strength, ds.p, cb)) != PVX_OK ||
+        (rc = device_to_host(ncands, dn.p, ib)) != PVX_OK || (rc = device_to_host(preferred, dq.p, ib)) != PVX_OK) return rc;
+    return nidx;
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

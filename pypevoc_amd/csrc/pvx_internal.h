@@ -268,6 +268,35 @@ int pvx_launch_reduce(const ReduceParams& p, int mode, hipStream_t s);
 // FuncWind's named reducers (func: pvx_funcwind_op); x complex128 when cpx (p.x then points at [n][2])
 int pvx_launch_funcwind(const ReduceParams& p, int func, bool cpx, hipStream_t s);
 
+// time-domain periodicity (k_period.hip, Periodicity.py:98-236).  Lag ranges lo[r]..hi[r] are the similarity lags a frame
+// reads; ns..ne the normaliser slice in the index space of the reference's array (amdf: lag; xcorr: nwind-1+lag).
+#define PVX_PERIOD_MAX_NCAND 64
+#define PVX_PERIOD_MAX_NWIND 32768
+struct PeriodParams {
+    const double* x;            // [nsamp] device
+    int64_t nsamp;
+    const double* wind;         // [nwind] device (filled in by pvx_period_run)
+    int nwind;
+    const int64_t* idx;         // [nfr] frame centres, device (filled in by pvx_period_run)
+    int64_t nfr;
+    int amdf, cand_method, mindelay, maxdelay, ncand;
+    double threshold, vthresh, fftthresh;
+    int lo[2], hi[2];
+    int ns, ne;
+    double* cand_period;        // [nfr][ncand]
+    double* cand_strength;
+    int32_t* ncands;            // [nfr]
+    int32_t* preferred;         // [nfr]
+    // filled in by pvx_period_run
+    const double* wnorm = nullptr;
+    double* xw_out = nullptr;
+    double* scratch = nullptr;
+    int* err = nullptr;
+};
+// p.x and the outputs are device memory; the window and the frame centres are host arrays (copied into a per-device
+// workspace the calls share, one at a time)
+int pvx_period_run(PeriodParams p, const double* h_wind, const int64_t* h_idx, hipStream_t s);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)
