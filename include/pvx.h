@@ -97,10 +97,13 @@ int64_t pvx_plan_workspace_bytes(const pvx_plan* plan);
  *   4  mode 1's arithmetic again (bit-identical results) with every wave on its own: a wave walks a contiguous range
  *      of rows DOWNWARDS over one spectrum buffer, the previous spectrum a frame's peaks need arrives one row later;
  *      sliding sample window at hop = nfft/4, nfft/2 (precision = 32, nfft in {512, 1024, 2048})
+ *   5  teams of mode 4's waves, 2 / 4 per frame (precision = 32, nfft in {4096, 8192}, npks <= 128); a call of 0x7fffff00
+ *      rows or more runs mode 0's path (the plan stays in mode 5)
  * Mode 0 itself runs as one launch for nfft in {512, 1024, 2048} (window + FFT + peaks: k_pv_rev at float64 with npks <= 64,
  * no spectrum workspace; k_stft_pv otherwise), as fused STFT + phase/peak kernel for nfft 4096 / 8192, and through rocFFT otherwise.
- * A new plan uses 4 where it is supported, else 5, else 0 (environment PVX_FFT_MODE overrides); 1, 2 and 3 are witness kernels of the
- * tests: the product library answers PVX_ERR_UNSUPPORTED for them (tests/libpvx_witness.so carries them).
+ * A new plan uses 4 where it is supported, else 5, else 0 (environment PVX_FFT_MODE overrides; the witness library tries 3 and 1
+ * before 5); 1, 2 and 3 are witness kernels of the tests: the product library answers PVX_ERR_UNSUPPORTED for them
+ * (tests/libpvx_witness.so carries them).
  */
 int pvx_plan_set_fft_mode(pvx_plan* plan, int mode);
 int pvx_plan_get_fft_mode(const pvx_plan* plan);
@@ -108,10 +111,11 @@ int pvx_plan_get_fft_mode(const pvx_plan* plan);
  * that takes a plan fails with PVX_ERR_INVALID when the calling thread is bound to another device (pvx_init(d), or a
  * pvx_batch worker's device) instead of running kernels on buffers of the wrong device. */
 int pvx_plan_device(const pvx_plan* plan);
-/* Which kernels the plan's last calls ran, as "analysis=<kernel>;tracker=<kernel>;synth=<kernel>" (a part is missing until its
- * call has run): k_fused_rev | k_fused_team | k_pv_rev | k_stft_pv | k_stft+k_phase_peaks | k_frames+rocfft+k_phase_peaks
- * for the analysis, k_synth_bodies<f64> | k_synth_bodies<f32> for the resynthesis.  For tests and benchmarks that must
- * know what they measured; the string lives in the plan and is valid until its next call. */
+/* Which kernels the plan's last calls ran, as "analysis=<kernel>;synth=<kernel>" (a part is missing until its call has run):
+ * k_fused_rev | k_fused_team | k_pv_rev | k_stft_pv | k_stft+k_phase_peaks | k_frames+rocfft+k_phase_peaks (the witness library
+ * also k_fused | k_fused_mw | k_fused_ring | k_pv_team) for the analysis, k_synth_bodies<f64> | k_synth_bodies<f32> for the
+ * resynthesis.  For tests and benchmarks that must know what they measured; the string lives in the plan and is valid until
+ * its next call. */
 const char* pvx_plan_last_kernels(const pvx_plan* plan);
 /*
  * Progress reporting: replaces Progress.update (pypevoc/ProgressDisplay.py:82-88), which the
@@ -125,9 +129,9 @@ int pvx_plan_set_progress(pvx_plan* plan, pvx_progress_fn fn, void* user);
 
 /*
  * Stage timing for bench.py's roofline line.  While enabled, hipEvents recorded on the launch
- * stream bracket every stage of every chunk.  pvx_plan_get_timing synchronises with those events
- * and returns, accumulated since the last call: ms[0] framing kernel, ms[1] rocFFT, ms[2]
- * phase/peak kernel, ms[3] fused kernel (fft modes 1-4, and mode 0's one-launch form); launches[i] = stage launches counted.
+ * stream bracket every stage of every chunk (of pvx_harmonic_analyze: its transform).  pvx_plan_get_timing synchronises with
+ * those events and returns, accumulated since the last call: ms[0] framing kernel (or k_stft), ms[1] rocFFT, ms[2]
+ * phase/peak kernel, ms[3] fused kernel (fft modes 1-5, and mode 0's one-launch form); launches[i] = stage launches counted.
  */
 int pvx_plan_set_timing(pvx_plan* plan, int enable);
 int pvx_plan_get_timing(pvx_plan* plan, double* ms /*[4]*/, int64_t* launches /*[4]*/);

@@ -142,13 +142,30 @@ extern "C" int64_t pvx_nframes(int64_t nsamp, int nfft, int hop) {
 }
 
 // ---- plan -----------------------------------------------------------------------------------
+// The analysis routes: which kernels one call of analyze_rows() runs (route_for() picks it), and pvx_plan_last_kernels' name
+// of each.  The fused kernels come first.
+enum class Route {
+    none,
+    fused, fused_mw, fused_ring, fused_rev, fused_team,   // fft modes 1 - 5: one float32 launch (k_fused*.hip)
+    pv_rev, pv_team,      // float64, one launch over all rows, the spectrum rows on chip (k_pv_rev.hip, k_pv_team.hip)
+    stft_pv,              // k_stft_pv.hip: window + FFT + peaks per chunk, the spectrum rows in the workspace
+    stft_peaks, stft_cand_peaks,   // k_stft -> k_phase_peaks; cand: the transform hands each row's candidate peaks on
+    frames_rocfft,        // k_frames -> rocFFT -> k_phase_peaks
+};
+static const char* const kRouteName[] = {"", "k_fused", "k_fused_mw", "k_fused_ring", "k_fused_rev", "k_fused_team", "k_pv_rev", "k_pv_team",
+                                         "k_stft_pv", "k_stft+k_phase_peaks", "k_stft+k_phase_peaks", "k_frames+rocfft+k_phase_peaks"};
+static_assert(sizeof(kRouteName) / sizeof(kRouteName[0]) == (size_t)Route::frames_rocfft + 1, "one name per route");
+static bool is_fused(Route r) { return r >= Route::fused && r <= Route::fused_team; }
+
 struct pvx_plan {
     int device = -1;          // the HIP device current when the plan was created: every buffer / stream / event below lives there
     double sr = 0, pkthresh = 0, wfact = 0, fstep = 0, dt = 0;
     int nfft = 0, hop = 0, npks = 0, N2 = 0, precision = 32, fft_mode = 0;
     int64_t max_rows = 0;     // rows per launch (without the halo row)
     bool rows_from_env = false;   // ... as PVX_MAX_ROWS set them
-    const char* last_analysis = nullptr;   // kernels of the last calls (pvx_plan_last_kernels)
+    Route general = Route::frames_rocfft;  // fft mode 0's route for the plan's shape and creation-time switches (route_for narrows
+                                           // it per call); all but frames_rocfft have k_stft write d_spec (has_stft)
+    Route last_route = Route::none;        // kernels of the last calls (pvx_plan_last_kernels)
     const char* last_synth = nullptr;
     std::string last_kernels;
     int64_t ldi = 0, ldo = 0; // workspace row pitches (elements / complex elements)
@@ -168,12 +185,7 @@ struct pvx_plan {
     rocfft_plan fft = nullptr;
     rocfft_execution_info info = nullptr;
     bool rocfft_ready = false;   // frames/spectrum workspace + rocFFT plan are created on first use
-    bool use_stft = false;       // float64, nfft 512..2048: k_stft writes the spectrum rows (no frame buffer, no rocFFT)
-    bool use_stft_pv = false;    // ... and finds the peaks in the same launch (k_stft_pv.hip)
-    bool use_pv_team = false;    // float64 at nfft 4096 / 8192, npks <= 64, hop nfft/4 or nfft/2: the same with a team of waves per frame (k_pv_team.hip)
-    bool use_pv_rev = false;     // ... without writing a spectrum row: rows walked downwards, the row at hand on chip (k_pv_rev.hip; npks <= 64)
-    double* d_lastspec = nullptr;   // k_pv_rev: [N2][2] the spectrum of the one row a call asks for (chunk carry, last_spec)
-    bool last_from_rev = false;  // the last analyze_rows() left its requested spectrum row in d_lastspec
+    double* d_lastspec = nullptr;   // k_pv_rev / k_pv_team: [N2][2] the spectrum of the one row a call asks for (chunk carry, last_spec)
     void* d_pvstage = nullptr;   // k_pv_rev at nfft 2048: the kept peaks' values between the frames (PvRevParams::stage)
     size_t pvstage_cap = 0;
     int wire_fmt = 1;            // the gather's wire format (k_wire.hip): 1 = f as float64, 2 = the float32 it is computed from (pvx_plan_set_wire_format)
@@ -185,7 +197,6 @@ struct pvx_plan {
     void* d_twiddle64 = nullptr; // complex<T>[nfft] W_nfft^j for k_stft (T = the plan's precision)
     void* d_twiddle = nullptr;   // float2[2048] W_2048^j for the fused kernel
     float* d_specrow = nullptr;  // 1024 complex: spectrum of one requested row (fused mode)
-    float* spec_host = nullptr;  // when set: the fused kernels write that row straight into this page-locked host block
     // PVHarmonic: per-frame f0 / previous-row tables and the carried spectrum of the last valid frame
     double* d_hf0 = nullptr;
     unsigned char* d_hx = nullptr;         // pvx_harmonic_analyze: the host signal's device copy (kept: allocating and freeing
@@ -246,7 +257,7 @@ extern "C" const char* pvx_plan_last_kernels(const pvx_plan* plan) {
     if (!plan) return "";
     pvx_plan* p = const_cast<pvx_plan*>(plan);
     p->last_kernels.clear();
-    if (p->last_analysis) { p->last_kernels += "analysis="; p->last_kernels += p->last_analysis; }
+    if (p->last_route != Route::none) { p->last_kernels += "analysis="; p->last_kernels += kRouteName[(int)p->last_route]; }
     if (p->last_synth) { if (!p->last_kernels.empty()) p->last_kernels += ";"; p->last_kernels += "synth="; p->last_kernels += p->last_synth; }
     return p->last_kernels.c_str();
 }
@@ -457,12 +468,13 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
         const void* src = precision == 64 ? (const void*)tw.data() : (const void*)twf.data();
         if (hipMalloc(&p->d_twiddle64, tw.size() * rs) != hipSuccess) { pvx_set_error("hipMalloc(stft twiddle) failed"); plan_free(p); return PVX_ERR_ALLOC; }
         if (hipMemcpy(p->d_twiddle64, src, tw.size() * rs, hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(stft twiddle) failed"); plan_free(p); return PVX_ERR_HIP; }
-        p->use_stft = true;
-        p->use_stft_pv = pvx_stft_pv_supported(nfft, precision, npks) != 0 && !getenv("PVX_NO_STFT_PV");
-        p->use_pv_rev = p->use_stft_pv && pvx_pv_rev_supported(nfft, precision, npks) != 0 && !getenv("PVX_NO_PV_REV");
+        // nfft 512 .. 2048: the peaks found in the transform's launch; at float64 with npks <= 64 the spectrum rows kept on chip
+        p->general = Route::stft_peaks;
+        if (pvx_stft_pv_supported(nfft, precision, npks) && !getenv("PVX_NO_STFT_PV"))
+            p->general = pvx_pv_rev_supported(nfft, precision, npks) && !getenv("PVX_NO_PV_REV") ? Route::pv_rev : Route::stft_pv;
         // (k_pv_team is a witness kernel -- tests/libpvx_witness.so, asked for with PVX_PV_TEAM=1: correct, one launch, and slower than
         // the two kernels it would replace, profiles/r06_ab_steps.txt; in the product library pvx_pv_team_supported() says no)
-        p->use_pv_team = precision == 64 && (nfft == 4096 || nfft == 8192) && npks <= 64 && getenv("PVX_PV_TEAM") != nullptr;
+        if (getenv("PVX_PV_TEAM") && pvx_pv_team_supported(nfft, precision, npks, hop)) p->general = Route::pv_team;
         if (!getenv("PVX_MAX_ROWS")) {
             int64_t big = (int64_t)(((size_t)1 << 30) / ((size_t)p->ldo * 2 * rs));
             if (big > 262144) big = 262144;
@@ -498,8 +510,7 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
     return PVX_OK;
 }
 
-// frames + spectrum workspace and the rocFFT plan (fft mode 0, calc_fft_frame): created on first use
-// spectrum workspace of the k_stft path: [max_rows+1][ldo] complex
+// spectrum workspace of the k_stft path: [max_rows+1][ldo] complex, created on first use
 static int ensure_spec_ws(pvx_plan* p) {
     if (p->d_spec) return PVX_OK;
     const size_t sbytes = (size_t)(p->max_rows + 1) * p->ldo * 2 * real_size(p->precision);
@@ -507,14 +518,33 @@ static int ensure_spec_ws(pvx_plan* p) {
     p->ws_bytes += (int64_t)sbytes;
     return PVX_OK;
 }
-// nfft 8192 on the general path (k_stft_split -> k_phase_peaks): the transform leaves every row's candidate peaks, the peak
-// kernel does not stream the 64 KB rows again (float64, config 2's signal: 0.79 -> 0.63 ms; PVX_NO_CAND=1: the two kernels
-// as before).  At nfft 4096 (teams of two waves at 256 registers: the scan's reads cannot all be in flight) the scan costs
-// the transform kernel what it saves the peak kernel: off unless PVX_CAND_4096=1.
-static bool plan_wants_cand(const pvx_plan* p) {
-    if (!p->use_stft || p->use_stft_pv || getenv("PVX_NO_CAND") != nullptr) return false;
-    return p->nfft == 8192 || (p->nfft == 4096 && getenv("PVX_CAND_4096") != nullptr);
+static bool has_stft(const pvx_plan* p) { return p->general != Route::frames_rocfft; }
+
+// The route of one call of analyze_rows() over `total_rows` rows of samples of type x_dtype: the plan's fft mode, else its
+// general route as far as the call allows.  The one-launch kernels index rows in 32 bits: a larger call of a team plan takes
+// the general path (for that call only), the float64 ones take k_stft_pv / k_stft.
+static Route route_for(const pvx_plan* p, int x_dtype, int64_t total_rows) {
+    const bool rows32 = total_rows < 0x7fffff00LL;
+    switch (p->fft_mode) {
+        case 1: return Route::fused;
+        case 2: return Route::fused_mw;
+        case 3: return Route::fused_ring;
+        case 4: return Route::fused_rev;
+        case 5: if (rows32) return Route::fused_team; break;
+    }
+    const Route g = p->general;
+    if (g == Route::pv_rev && rows32 && pvx_pv_rev_takes(p->nfft, x_dtype, p->hop)) return Route::pv_rev;
+    if (g == Route::pv_team && rows32) return Route::pv_team;
+    if (g == Route::pv_rev || g == Route::stft_pv) return pvx_stft_pv_takes(p->nfft, p->precision, x_dtype, p->hop) ? Route::stft_pv : Route::stft_peaks;
+    if (g == Route::frames_rocfft) return g;
+    // nfft 8192 (k_stft_split -> k_phase_peaks): the transform leaves every row's candidate peaks, the peak kernel does not
+    // stream the 64 KB rows again (float64, config 2's signal: 0.79 -> 0.63 ms; PVX_NO_CAND=1: the two kernels as before).  At
+    // nfft 4096 (teams of two waves at 256 registers: the scan's reads cannot all be in flight) the scan costs the transform
+    // kernel what it saves the peak kernel: off unless PVX_CAND_4096=1.
+    const bool cand = getenv("PVX_NO_CAND") == nullptr && (p->nfft == 8192 || (p->nfft == 4096 && getenv("PVX_CAND_4096") != nullptr));
+    return cand ? Route::stft_cand_peaks : Route::stft_peaks;
 }
+
 static int ensure_cand_ws(pvx_plan* p) {
     if (p->d_cand_bin) return PVX_OK;
     const int cap = p->N2 / 2 + 8;
@@ -541,7 +571,7 @@ static void release_rocfft(pvx_plan* p) {
     if (p->d_frames) { (void)hipFree(p->d_frames); p->d_frames = nullptr; }
     if (p->d_rspec) { (void)hipFree(p->d_rspec); p->d_rspec = nullptr; }
     if (p->d_work) { (void)hipFree(p->d_work); p->d_work = nullptr; }
-    if (!p->rocfft_small && !p->use_stft && p->d_spec) { (void)hipFree(p->d_spec); p->d_spec = nullptr; }
+    if (!p->rocfft_small && !has_stft(p) && p->d_spec) { (void)hipFree(p->d_spec); p->d_spec = nullptr; }
     p->rocfft_ready = false; p->rocfft_small = false; p->work_bytes = 0;
 }
 
@@ -552,7 +582,7 @@ static int ensure_rocfft(pvx_plan* p, bool full) {
     if (p->rocfft_ready) release_rocfft(p);
     const int nfft = p->nfft, precision = p->precision;
     const size_t rs = real_size(precision);
-    const bool small = !full || p->use_stft;
+    const bool small = !full || has_stft(p);
     const int64_t max_rows = small ? 2 : p->max_rows;
     const int64_t ws_rows = max_rows + 1;
     p->rocfft_rows = max_rows;
@@ -652,17 +682,43 @@ extern "C" int pvx_plan_get_timing(pvx_plan* plan, double* ms, int64_t* launches
 }
 
 // ---- run_pv ---------------------------------------------------------------------------------
+// the spectrum row a call asks for (chunk carry, last_spec; -1: none), and a page-locked block the fused kernels write it to
+// instead of d_specrow
+struct SpecRequest { int64_t row = -1; float* host = nullptr; };
+
+// where `route` left the spectrum row its call asked for (the call's last row `row`): [N2] complex, float32 or float64
+struct SpecRow { const void* d; bool f32; };
+static SpecRow spec_row_at(const pvx_plan* p, Route route, int64_t row) {
+    if (is_fused(route)) return {p->d_specrow, true};
+    if (route == Route::pv_rev || route == Route::pv_team) return {p->d_lastspec, false};
+    const int64_t wsrow = row % p->max_rows + 1;             // in the last chunk's workspace
+    return {(const char*)p->d_spec + (size_t)wsrow * p->ldo * 2 * real_size(p->precision), p->precision == 32};
+}
+
+// window + FFT of a chunk's workspace rows into d_spec: k_stft, or k_frames + rocFFT (stage events 0 and 1)
+static int launch_transform(pvx_plan* p, const FrameParams& fp, int x_dtype, hipStream_t s) {
+    int rc;
+    if ((rc = plan_event(p, s, 0)) != PVX_OK) return rc;
+    if (has_stft(p)) return pvx_launch_stft(fp, p->d_spec, p->ldo, p->d_twiddle64, x_dtype, p->precision, s);
+    if ((rc = pvx_launch_frames(fp, x_dtype, p->precision, s)) != PVX_OK || (rc = plan_event(p, s, 1)) != PVX_OK) return rc;
+    void* in[1] = {p->d_frames}, *out[1] = {p->d_spec};
+    PVX_FFT_CHECK(rocfft_execution_info_set_stream(p->info, s));
+    PVX_FFT_CHECK(rocfft_execute(p->fft, in, out, p->info));
+    return PVX_OK;
+}
+
 template <typename T> static int grow_dev(T** p, size_t* cap, size_t need);
-static int analyze_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsamp, int64_t nsig, int64_t sig_stride,
+// The analysis of a call by `route` (route_for), which the plan records.  wire_out: d_f / d_mag / d_ph / d_binno / d_totalmag
+// are the sections of a wire block (pvx_analyze_dev_wire): only k_fused_rev writes it itself.
+static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, int64_t nsamp, int64_t nsig, int64_t sig_stride,
                         int64_t F, double* d_f, double* d_mag, double* d_ph, double* d_realph, double* d_binno,
                         double* d_t, double* d_totalmag, const double* d_prev0, hipStream_t s,
-                        int64_t spec_row = -1, bool wire_out = false) {
+                        SpecRequest spec = {}, bool wire_out = false) {
     const int64_t total_rows = nsig * (F + 1);
     int rc;
-    // wire_out: d_f / d_mag / d_ph / d_binno / d_totalmag are the sections of a wire block (pvx_analyze_dev_wire): only the kernels
-    // that write it themselves take such a call
-    if (wire_out && !(p->fft_mode == 4 && p->precision == 32)) return PVX_ERR_UNSUPPORTED;
-    if (p->fft_mode >= 1 && p->fft_mode <= 5) {
+    if (wire_out && route != Route::fused_rev) return PVX_ERR_UNSUPPORTED;
+    p->last_route = route;
+    if (is_fused(route)) {
         // one launch: window + FFT + peaks, no intermediate arrays (k_fused_rev.hip / k_fused_team.hip; the witnesses' modes 1 - 3)
         if (x_dtype == PVX_F64) {
             // float64 samples already in HBM (the host entry points narrow while they stage): the fused kernels' first step
@@ -680,11 +736,11 @@ static int analyze_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsamp
         fp.wfbin = p->d_wfbin; fp.prev0 = d_prev0;
         fp.f = d_f; fp.mag = d_mag; fp.ph = d_ph; fp.realph = d_realph; fp.binno = d_binno;
         fp.t = d_t; fp.totalmag = d_totalmag; fp.win = p->d_win; fp.twiddle = p->d_twiddle;
-        fp.spec_out = spec_row >= 0 ? (p->spec_host ? p->spec_host : p->d_specrow) : nullptr; fp.spec_row = spec_row;
+        fp.spec_out = spec.row >= 0 ? (spec.host ? spec.host : p->d_specrow) : nullptr; fp.spec_row = spec.row;
         fp.blocks_override = p->fused_blocks;
         fp.stash = nullptr; fp.stash_bytes = 0;
         fp.wire = wire_out ? p->wire_fmt : 0;
-        if (p->fft_mode == 4) {
+        if (route == Route::fused_rev) {
             // k_fused_rev: the block where its waves hand a spectrum to the wave below them (sized once, for a full grid)
             if (!p->d_stash) {
                 FusedParams q = fp;
@@ -696,26 +752,19 @@ static int analyze_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsamp
             fp.stash = p->d_stash; fp.stash_bytes = p->stash_cap;
         }
         if ((rc = plan_event(p, s, 3)) != PVX_OK) return rc;
-        rc = (p->fft_mode == 1) ? pvx_launch_fused(fp, p->nfft, x_dtype, s)
-           : (p->fft_mode == 2) ? pvx_launch_fused_mw(fp, p->nfft, x_dtype, s)
-           : (p->fft_mode == 3) ? pvx_launch_fused_ring(fp, p->nfft, x_dtype, s)
-           : (p->fft_mode == 5) ? pvx_launch_fused_team(fp, p->nfft, x_dtype, s) : pvx_launch_fused_rev(fp, p->nfft, x_dtype, s);
-        // (what the plan could not know when it chose the team kernel -- a salience radius beyond its fetch, a row count
-        // beyond 32 bits -- goes to the general path below instead of failing the call)
-        p->last_analysis = p->fft_mode == 1 ? "k_fused" : p->fft_mode == 2 ? "k_fused_mw" : p->fft_mode == 3 ? "k_fused_ring" : p->fft_mode == 5 ? "k_fused_team" : "k_fused_rev";
-        if (rc == PVX_ERR_UNSUPPORTED && p->fft_mode == 5 && !wire_out) {
-            p->fft_mode = 0;                                       // (the plan stays there: what carries a spectrum between calls asks the mode)
-        } else {
-            if (rc != PVX_OK) return rc;
-            return plan_event(p, s, -1);
+        switch (route) {
+            case Route::fused: rc = pvx_launch_fused(fp, p->nfft, x_dtype, s); break;
+            case Route::fused_mw: rc = pvx_launch_fused_mw(fp, p->nfft, x_dtype, s); break;
+            case Route::fused_ring: rc = pvx_launch_fused_ring(fp, p->nfft, x_dtype, s); break;
+            case Route::fused_team: rc = pvx_launch_fused_team(fp, p->nfft, x_dtype, s); break;
+            default: rc = pvx_launch_fused_rev(fp, p->nfft, x_dtype, s); break;
         }
+        return rc != PVX_OK ? rc : plan_event(p, s, -1);
     }
-    p->last_from_rev = false;
-    const bool take_rev = p->use_stft && p->use_pv_rev && pvx_pv_rev_takes(p->nfft, x_dtype, p->hop) && total_rows < 0x7fffff00LL;
-    const bool take_team = p->use_stft && p->use_pv_team && pvx_pv_team_supported(p->nfft, p->precision, p->npks, p->hop) != 0 && total_rows < 0x7fffff00LL;
-    if (take_rev || take_team) {
+    if (route == Route::pv_rev || route == Route::pv_team) {
         // float64, npks <= 64: ONE launch over all rows, no spectrum workspace -- nfft 512 .. 2048: a wave per frame (k_pv_rev.hip);
         // nfft 4096 / 8192 at the sliding-window hops: a team of waves per frame (k_pv_team.hip)
+        const bool team = route == Route::pv_team;
         PvRevParams rp;
         rp.x = d_x; rp.sig_stride = sig_stride; rp.F = F; rp.total_rows = total_rows;
         rp.hop = p->hop; rp.K = p->npks; rp.rad = 5;                                     // PV.py:177
@@ -723,16 +772,16 @@ static int analyze_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsamp
         rp.wfbin = p->d_wfbin; rp.prev0 = d_prev0;
         rp.f = d_f; rp.mag = d_mag; rp.ph = d_ph; rp.realph = d_realph; rp.binno = d_binno;
         rp.t = d_t; rp.totalmag = d_totalmag; rp.win = p->d_win; rp.twiddle = p->d_twiddle64;
-        rp.spec_out = nullptr; rp.spec_row = -1;
-        if (spec_row >= 0) {
+        rp.spec_out = nullptr; rp.spec_row = spec.row;
+        if (spec.row >= 0) {
             if (!p->d_lastspec) PVX_HIP_CHECK(hipMalloc((void**)&p->d_lastspec, sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1)));
-            rp.spec_out = p->d_lastspec; rp.spec_row = spec_row;
+            rp.spec_out = p->d_lastspec;
         }
         rp.blocks_override = 0;
         if (const char* e = getenv("PVX_PV_REV_BLOCKS")) { const long long v = atoll(e); if (v >= 1) rp.blocks_override = v; }   // tests: other grids
         rp.win_symmetric = p->win_symmetric ? 1 : 0;
         rp.stage = nullptr; rp.stage_bytes = 0;
-        const size_t need = take_team ? pvx_pv_team_stage_bytes(p->nfft) : pvx_pv_rev_stage_bytes(p->nfft);
+        const size_t need = team ? pvx_pv_team_stage_bytes(p->nfft) : pvx_pv_rev_stage_bytes(p->nfft);
         if (need > 0) {
             if ((rc = grow_dev(&p->d_pvstage, &p->pvstage_cap, need)) != PVX_OK) return rc;
             rp.stage = p->d_pvstage; rp.stage_bytes = p->pvstage_cap;
@@ -742,20 +791,15 @@ static int analyze_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsamp
         for (int64_t R0 = 0; R0 < total_rows; R0 += piece) {
             rp.row_begin = R0; rp.row_end = (total_rows - R0 < piece) ? total_rows : R0 + piece;
             if ((rc = plan_event(p, s, 3)) != PVX_OK) return rc;
-            if ((rc = take_team ? pvx_launch_pv_team(rp, p->nfft, x_dtype, s) : pvx_launch_pv_rev(rp, p->nfft, x_dtype, s)) != PVX_OK) return rc;
+            if ((rc = team ? pvx_launch_pv_team(rp, p->nfft, x_dtype, s) : pvx_launch_pv_rev(rp, p->nfft, x_dtype, s)) != PVX_OK) return rc;
             if ((rc = plan_event(p, s, -1)) != PVX_OK) return rc;
             if ((rc = plan_progress(p, s, rp.row_end, total_rows, nsig)) != PVX_OK) return rc;
         }
-        p->last_from_rev = spec_row >= 0;
-        p->last_analysis = take_team ? "k_pv_team" : "k_pv_rev";
         return PVX_OK;
     }
-    if (p->use_stft) { if ((rc = ensure_spec_ws(p)) != PVX_OK) return rc; }
-    else {
-        if ((rc = ensure_rocfft(p, true)) != PVX_OK) return rc;
-        PVX_FFT_CHECK(rocfft_execution_info_set_stream(p->info, s));
-    }
-    const bool cand = plan_wants_cand(p);
+    // chunks of max_rows rows through the spectrum workspace
+    if ((rc = has_stft(p) ? ensure_spec_ws(p) : ensure_rocfft(p, true)) != PVX_OK) return rc;
+    const bool cand = route == Route::stft_cand_peaks;
     if (cand && (rc = ensure_cand_ws(p)) != PVX_OK) return rc;
     for (int64_t R0 = 0; R0 < total_rows; R0 += p->max_rows) {
         const int64_t nrows = (total_rows - R0 < p->max_rows) ? (total_rows - R0) : p->max_rows;
@@ -774,30 +818,16 @@ static int analyze_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsamp
             fp.cand_y = p->d_cand_y; fp.cand_bin = p->d_cand_bin; fp.cand_stats = p->d_cand_stats; fp.cand_cap = p->cand_cap; fp.cand_thr = p->pkthresh;
             pp.cand_y = p->d_cand_y; pp.cand_bin = p->d_cand_bin; pp.cand_stats = p->d_cand_stats; pp.cand_cap = p->cand_cap;
         }
-        if (p->use_stft && p->use_stft_pv && pvx_stft_pv_takes(p->nfft, p->precision, x_dtype, p->hop)) {
+        if (route == Route::stft_pv) {
             // window + FFT + untangle + peaks of every row in one kernel (k_stft_pv.hip); the spectrum rows still land in
             // the workspace
             if ((rc = plan_event(p, s, 3)) != PVX_OK) return rc;
             if ((rc = pvx_launch_stft_pv(fp, pp, p->d_spec, p->ldo, p->d_twiddle64, x_dtype, p->precision, s)) != PVX_OK) return rc;
-            if ((rc = plan_event(p, s, -1)) != PVX_OK) return rc;
-            if ((rc = plan_progress(p, s, R0 + nrows, total_rows, nsig)) != PVX_OK) return rc;
-            p->last_analysis = "k_stft_pv";
-            continue;
-        }
-        if ((rc = plan_event(p, s, 0)) != PVX_OK) return rc;
-        if (p->use_stft) {
-            // window + FFT + untangle of every workspace row in one kernel (k_stft.hip)
-            if ((rc = pvx_launch_stft(fp, p->d_spec, p->ldo, p->d_twiddle64, x_dtype, p->precision, s)) != PVX_OK) return rc;
         } else {
-            if ((rc = pvx_launch_frames(fp, x_dtype, p->precision, s)) != PVX_OK) return rc;
-            if ((rc = plan_event(p, s, 1)) != PVX_OK) return rc;
-            void* in[1] = {p->d_frames};
-            void* out[1] = {p->d_spec};
-            PVX_FFT_CHECK(rocfft_execute(p->fft, in, out, p->info));
+            if ((rc = launch_transform(p, fp, x_dtype, s)) != PVX_OK) return rc;
+            if ((rc = plan_event(p, s, 2)) != PVX_OK) return rc;
+            if ((rc = pvx_launch_phase_peaks(pp, p->precision, s)) != PVX_OK) return rc;
         }
-        if ((rc = plan_event(p, s, 2)) != PVX_OK) return rc;
-        if ((rc = pvx_launch_phase_peaks(pp, p->precision, s)) != PVX_OK) return rc;
-        p->last_analysis = p->use_stft ? "k_stft+k_phase_peaks" : "k_frames+rocfft+k_phase_peaks";
         if ((rc = plan_event(p, s, -1)) != PVX_OK) return rc;
         if ((rc = plan_progress(p, s, R0 + nrows, total_rows, nsig)) != PVX_OK) return rc;
     }
@@ -826,8 +856,8 @@ extern "C" int64_t pvx_analyze_dev(pvx_plan* p, const void* d_x, int x_dtype, in
     const int64_t F = pvx_nframes(nsamp, p->nfft, p->hop);
     if (F == 0) return 0;
     if (!d_f || !d_mag || !d_ph || !d_realph || !d_binno) { pvx_set_error("null output array"); return PVX_ERR_INVALID; }
-    rc = analyze_rows(p, d_x, x_dtype, nsamp, nsig, sig_stride, F, d_f, d_mag, d_ph, d_realph, d_binno, d_t,
-                      d_totalmag, d_prev0, (hipStream_t)stream);
+    rc = analyze_rows(p, route_for(p, x_dtype, nsig * (F + 1)), d_x, x_dtype, nsamp, nsig, sig_stride, F, d_f, d_mag, d_ph,
+                      d_realph, d_binno, d_t, d_totalmag, d_prev0, (hipStream_t)stream);
     return rc == PVX_OK ? F : rc;
 }
 
@@ -1025,15 +1055,10 @@ static const size_t kSmallCall = (size_t)4 << 20;     // calls up to this size g
 // (pvx_batch_run's workers; the process-wide bounce ring in between cost a 30-s signal 0.45 ms alone and serialised them)
 static const size_t kSmallAnalyze = kStageMin;
 
-// spectrum of the last row of the launch that just ran on `s` -> p->d_prev (float64 [N2][2])
-static int carry_spectrum(pvx_plan* p, int64_t rows_in_call, hipStream_t s) {
-    if (!p->d_prev) PVX_HIP_CHECK(hipMalloc((void**)&p->d_prev, sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1)));
-    if (p->fft_mode != 0) return pvx_launch_spec_to_prev(p->d_prev, p->d_specrow, 2 * p->N2, 1, s);
-    if (p->last_from_rev) return pvx_launch_spec_to_prev(p->d_prev, p->d_lastspec, 2 * p->N2, 0, s);
-    const int64_t lastR0 = ((rows_in_call - 1) / p->max_rows) * p->max_rows;
-    const int64_t wsrow = (rows_in_call - 1) - lastR0 + 1;
-    const size_t rs = real_size(p->precision);
-    return pvx_launch_spec_to_prev(p->d_prev, (const char*)p->d_spec + (size_t)wsrow * p->ldo * 2 * rs, 2 * p->N2, p->precision == 32, s);
+// spectrum of the last row of the call that just ran on `s` by `route` -> p->d_prev (float64 [N2][2])
+static int carry_spectrum(pvx_plan* p, Route route, int64_t rows_in_call, hipStream_t s) {
+    const SpecRow r = spec_row_at(p, route, rows_in_call - 1);
+    return pvx_launch_spec_to_prev(p->d_prev, r.d, 2 * p->N2, r.f32, s);
 }
 
 // The host entry point of run_pv (PV.py:213-264).
@@ -1066,9 +1091,7 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
     if (keep) {
         if ((rc = grow_dev(&p->d_res, &p->res_cap, (size_t)nsig * F * per_frame_out)) != PVX_OK) return rc;
     }
-    {
-        if (!p->d_prev) PVX_HIP_CHECK(hipMalloc((void**)&p->d_prev, sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1)));
-    }
+    if (!p->d_prev) PVX_HIP_CHECK(hipMalloc((void**)&p->d_prev, sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1)));
     if (prev0) PVX_HIP_CHECK(hipMemcpyAsync(p->d_prev, prev0, sizeof(double) * 2 * p->N2, hipMemcpyHostToDevice, s));
 
     // ---- chunking: units are frames of the one signal, or whole signals of a batch
@@ -1103,10 +1126,12 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
     const size_t total_in = (size_t)((nsig - 1) * sig_stride + nsamp) * es;
     const size_t total_out = (size_t)nsig * F * per_frame_out;
     const bool small = nchunks == 1 && total_in + (keep ? 0 : total_out) <= kSmallAnalyze;
+    // a small call's pinned block: the staged input | the result block at out_off | the last spectrum at spec_off
+    const size_t spec_pin = (size_t)(p->N2 > 0 ? p->N2 : 1) * 16 + 256;
+    const size_t out_off = (total_in + 255) & ~(size_t)255, spec_off = (out_off + (keep ? 0 : total_out) + 255) & ~(size_t)255;
     // a float64 signal analysed at precision 32: every kernel's first step is (float)x[n], so the host side narrows while it
     // stages (same rounding, half the bytes over PCIe, the aligned float loads on the device) -- on the small-call path and
     // in the staging threads of the large one
-    const size_t spec_pin = (size_t)(p->N2 > 0 ? p->N2 : 1) * 16 + 256;       // the last spectrum lands behind the staged data
     const bool narrow = p->precision == 32 && x_dtype == PVX_F64;
     const int dev_dtype = narrow ? PVX_F32 : x_dtype;
     const size_t des = narrow ? 4 : es;
@@ -1144,6 +1169,8 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
 
     p->progress_live = true;
     int64_t last_rows = 0;
+    Route route = Route::none;                 // the last chunk's route and spectrum request
+    SpecRequest spec;
     tr.mark("setup");
     for (int64_t c = 0; c < nchunks; c++) {
         const int b = (int)(c & 1);
@@ -1160,7 +1187,7 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
             ob = p->d_out[b];
         }
         if (small) {
-            if ((rc = grow_pin(p, ((total_in + 255) & ~(size_t)255) + (keep ? 0 : total_out) + spec_pin)) != PVX_OK) { p->progress_live = false; return rc; }
+            if ((rc = grow_pin(p, out_off + (keep ? 0 : total_out) + spec_pin)) != PVX_OK) { p->progress_live = false; return rc; }
             // staged in pieces: the DMA of piece i runs under the host copy of piece i+1
             const size_t nel = in_bytes / es, piece = (size_t)64 << 10;
             for (size_t e0 = 0; e0 < nel; e0 += piece) {
@@ -1193,22 +1220,17 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
             d = block_ptrs(ob, c_frames, K);
             d.t = nullptr;
         }
-        const bool want_spec = (c + 1 < nchunks && by_frames) || (last_spec && c + 1 == nchunks);
-        // small call, fused kernels: the last spectrum is written by the kernel itself into the pinned block (one
-        // 16 KB burst over PCIe instead of a separate copy operation behind the kernel)
-        float* spec_host = nullptr;
-        if (small && last_spec && p->fft_mode != 0) {
-            spec_host = (float*)((unsigned char*)p->h_pin + ((((total_in + 255) & ~(size_t)255) + (keep ? 0 : total_out) + 255) & ~(size_t)255));
-            if ((size_t)((unsigned char*)spec_host - (unsigned char*)p->h_pin) + (size_t)p->N2 * 8 > p->pin_cap) spec_host = nullptr;
-        }
-        p->spec_host = spec_host;
         const double* dprev = (c > 0 && by_frames) || prev0 ? p->d_prev : nullptr;
         last_rows = c_nsig * (c_frames / c_nsig + 1);
-        rc = analyze_rows(p, p->d_in[b], dev_dtype, c_nsamp, c_nsig, by_frames ? c_nsamp : sig_stride, c_frames / c_nsig,
-                          d.f, d.mag, d.ph, d.realph, d.binno, d.t, d.totalmag, dprev, s, want_spec ? last_rows - 1 : -1);
-        p->spec_host = nullptr;
+        route = route_for(p, dev_dtype, last_rows);
+        spec = SpecRequest{(c + 1 < nchunks && by_frames) || (last_spec && c + 1 == nchunks) ? last_rows - 1 : -1};
+        // small call, fused kernels: the last spectrum is written by the kernel itself into the pinned block (one
+        // 16 KB burst over PCIe instead of a separate copy operation behind the kernel)
+        if (small && last_spec && is_fused(route) && spec_off + (size_t)p->N2 * 8 <= p->pin_cap) spec.host = (float*)((unsigned char*)p->h_pin + spec_off);
+        rc = analyze_rows(p, route, p->d_in[b], dev_dtype, c_nsamp, c_nsig, by_frames ? c_nsamp : sig_stride, c_frames / c_nsig,
+                          d.f, d.mag, d.ph, d.realph, d.binno, d.t, d.totalmag, dprev, s, spec);
         tr.mark("kernels issued");
-        if (rc == PVX_OK && c + 1 < nchunks && by_frames) rc = carry_spectrum(p, last_rows, s);
+        if (rc == PVX_OK && c + 1 < nchunks && by_frames) rc = carry_spectrum(p, route, last_rows, s);
         if (rc != PVX_OK) { p->progress_live = false; return rc; }
         PVX_HIP_CHECK(hipEventRecord(p->ev_done[b], s));
         if (!keep && !small && c >= 1) {
@@ -1227,7 +1249,7 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
         p->res_F = F; p->res_nsig = nsig; p->res_valid = true;
     } else if (small) {
         // one D2H of the whole block into pinned memory, one synchronisation, then plain memcpys
-        double* hb = (double*)((char*)p->h_pin + ((total_in + 255) & ~(size_t)255));
+        double* hb = (double*)((char*)p->h_pin + out_off);
         PVX_HIP_CHECK(hipMemcpyAsync(hb, p->d_out[0], total_out, hipMemcpyDeviceToHost, s));
         PVX_HIP_CHECK(hipStreamSynchronize(s));
         const HostOut h = block_ptrs(hb, nsig * F, K);
@@ -1242,41 +1264,27 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
         for (int64_t b = 0; b < nsig; b++)
             for (int64_t fr = 0; fr < F; fr++) ho->t[b * F + fr] = ((double)(fr * (int64_t)p->hop) + p->nfft / 2.0) / p->sr;   // PV.py:247
     }
-    // the spectrum of the last frame (PV.oldfft after the loop, PV.py:209): float [N2][2] from the fused kernels,
-    // or the last chunk's last row of the general path's workspace
-    const size_t rs = real_size(p->fft_mode != 0 ? 32 : p->precision);
-    const void* d_last = nullptr;
-    if (last_spec && p->fft_mode != 0) d_last = p->d_specrow;
-    else if (last_spec && p->last_from_rev) d_last = p->d_lastspec;
-    else if (last_spec) {
-        const int64_t lastR0 = ((last_rows - 1) / p->max_rows) * p->max_rows;
-        const int64_t wsrow = (last_rows - 1) - lastR0 + 1;
-        d_last = (const char*)p->d_spec + (size_t)wsrow * p->ldo * 2 * rs;
+    // the spectrum of the last frame (PV.oldfft after the loop, PV.py:209), where the last chunk's route left it: in the pinned
+    // block already when the fused kernel wrote it there; a small call's copy goes there too, under the one synchronisation below
+    const SpecRow last = last_spec ? spec_row_at(p, route, last_rows - 1) : SpecRow{nullptr, false};
+    const size_t last_bytes = (size_t)p->N2 * 2 * (last.f32 ? 4 : 8);
+    unsigned char* h_last = (unsigned char*)spec.host;
+    if (last_spec && small && !h_last && spec_off + last_bytes <= p->pin_cap) {
+        h_last = (unsigned char*)p->h_pin + spec_off;
+        PVX_HIP_CHECK(hipMemcpyAsync(h_last, last.d, last_bytes, hipMemcpyDeviceToHost, s));
     }
-    std::vector<unsigned char> tmp;
-    unsigned char* h_last = nullptr;
-    bool by_kernel = false;
-    if (d_last && small && p->fft_mode != 0) {
-        unsigned char* q = (unsigned char*)p->h_pin + ((((total_in + 255) & ~(size_t)255) + (keep ? 0 : total_out) + 255) & ~(size_t)255);
-        if ((size_t)(q - (unsigned char*)p->h_pin) + (size_t)p->N2 * 8 <= p->pin_cap) { h_last = q; by_kernel = true; }   // as decided before the launch
-    }
-    if (d_last && small && !by_kernel) {
-        // small call: into the pinned block behind the staged data, under the one synchronisation below
-        h_last = (unsigned char*)p->h_pin + ((((total_in + 255) & ~(size_t)255) + (keep ? 0 : total_out) + 255) & ~(size_t)255);
-        if ((size_t)(h_last - (unsigned char*)p->h_pin) + (size_t)p->N2 * 2 * rs > p->pin_cap) h_last = nullptr;
-    }
-    if (h_last && !by_kernel) PVX_HIP_CHECK(hipMemcpyAsync(h_last, d_last, (size_t)p->N2 * 2 * rs, hipMemcpyDeviceToHost, s));
     tr.mark("tail issued");
     PVX_HIP_CHECK(hipStreamSynchronize(s));
     tr.mark("synchronised");
-    if (d_last) {
+    if (last_spec) {
+        std::vector<unsigned char> tmp;
         if (!h_last) {
-            tmp.resize((size_t)p->N2 * 2 * rs);
+            tmp.resize(last_bytes);
             h_last = tmp.data();
-            PVX_HIP_CHECK(hipMemcpy(h_last, d_last, tmp.size(), hipMemcpyDeviceToHost));
+            PVX_HIP_CHECK(hipMemcpy(h_last, last.d, last_bytes, hipMemcpyDeviceToHost));
         }
         for (int i = 0; i < 2 * p->N2; i++)
-            last_spec[i] = rs == 4 ? (double)((const float*)h_last)[i] : ((const double*)h_last)[i];
+            last_spec[i] = last.f32 ? (double)((const float*)h_last)[i] : ((const double*)h_last)[i];
     }
     if (p->progress_fn) p->progress_fn(nsig * F, nsig * F, p->progress_user);
     return F;
@@ -1874,8 +1882,7 @@ static int harmonic_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsam
                          double fmin, double* d_f, double* d_mag, double* d_ph, double* d_res, double* d_t,
                          const double* d_prev0, hipStream_t s, bool* any_valid) {
     int rc;
-    if (p->use_stft) { if ((rc = ensure_spec_ws(p)) != PVX_OK) return rc; }
-    else if ((rc = ensure_rocfft(p, true)) != PVX_OK) return rc;
+    if ((rc = has_stft(p) ? ensure_spec_ws(p) : ensure_rocfft(p, true)) != PVX_OK) return rc;
     const size_t rs = real_size(p->precision);
     // previous-valid-frame table (PV.py:509, 491: oldfft only moves on analysed frames)
     std::vector<int32_t> prow((size_t)F);
@@ -1908,7 +1915,6 @@ static int harmonic_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsam
     PVX_HIP_CHECK(hipMemcpyAsync(p->d_hf0, f0, (size_t)F * 8, hipMemcpyHostToDevice, s));
     PVX_HIP_CHECK(hipMemcpyAsync(p->d_hprev, prow.data(), (size_t)F * 4, hipMemcpyHostToDevice, s));
     PVX_HIP_CHECK(hipStreamSynchronize(s));                              // prow is a local
-    if (!p->use_stft) PVX_FFT_CHECK(rocfft_execution_info_set_stream(p->info, s));
     const int64_t total_rows = F + 1;
     for (int64_t R0 = 0; R0 < total_rows; R0 += p->max_rows) {
         const int64_t nrows = (total_rows - R0 < p->max_rows) ? (total_rows - R0) : p->max_rows;
@@ -1916,14 +1922,7 @@ static int harmonic_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsam
         fp.x = d_x; fp.nsamp = nsamp; fp.sig_stride = nsamp; fp.F = F; fp.R0 = R0;
         fp.ws_rows = nrows + 1; fp.total_rows = total_rows; fp.nfft = p->nfft; fp.hop = p->hop;
         fp.win = p->d_win; fp.frames = p->d_frames; fp.ldi = p->ldi;
-        if (p->use_stft) {
-            if ((rc = pvx_launch_stft(fp, p->d_spec, p->ldo, p->d_twiddle64, x_dtype, p->precision, s)) != PVX_OK) return rc;
-        } else {
-            if ((rc = pvx_launch_frames(fp, x_dtype, p->precision, s)) != PVX_OK) return rc;
-            void* in[1] = {p->d_frames};
-            void* out[1] = {p->d_spec};
-            PVX_FFT_CHECK(rocfft_execute(p->fft, in, out, p->info));
-        }
+        if ((rc = launch_transform(p, fp, x_dtype, s)) != PVX_OK || (rc = plan_event(p, s, -1)) != PVX_OK) return rc;
         HarmParams hp;
         hp.spec = p->d_spec; hp.ldo = p->ldo;
         hp.fr_begin = (R0 > 1 ? R0 : 1) - 1;
@@ -2290,7 +2289,8 @@ extern "C" int64_t pvx_analyze_dev_wire(pvx_plan* p, const void* d_x, int x_dtyp
     const size_t n = (size_t)rows * (size_t)p->npks, ts = p->precision == 64 ? 8 : 4;
     auto al8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
     unsigned char* w = (unsigned char*)d_wire;
-    if (p->fft_mode == 4 && p->precision == 32 && getenv("PVX_NO_WIRE_OUT") == nullptr) {
+    const Route route = route_for(p, x_dtype, nsig * (F + 1));
+    if (route == Route::fused_rev && getenv("PVX_NO_WIRE_OUT") == nullptr) {
         // the sections of the block (k_wire.hip) as the kernel's output arrays
         const size_t fw = p->wire_fmt == 2 ? 4 : 8;                   // (format 2: the float32 the frequency is computed from)
         double* wf = (double*)w;
@@ -2298,13 +2298,13 @@ extern "C" int64_t pvx_analyze_dev_wire(pvx_plan* p, const void* d_x, int x_dtyp
         double* wp = (double*)(w + al8(n * fw) + al8(n * ts));
         double* wb = (double*)(w + al8(n * fw) + 2 * al8(n * ts));
         double* wt = (double*)(w + al8(n * fw) + 2 * al8(n * ts) + al8(n * 2));
-        rc = analyze_rows(p, d_x, x_dtype, nsamp, nsig, sig_stride, F, wf, wm, wp, nullptr, wb, nullptr, wt, nullptr, (hipStream_t)stream, -1, true);
+        rc = analyze_rows(p, route, d_x, x_dtype, nsamp, nsig, sig_stride, F, wf, wm, wp, nullptr, wb, nullptr, wt, nullptr, (hipStream_t)stream, {}, true);
         return rc == PVX_OK ? F : rc;
     }
     const size_t per_frame_out = (size_t)(5 * p->npks + 2) * sizeof(double);
     if ((rc = grow_dev(&p->d_wiretmp, &p->wiretmp_cap, (size_t)rows * per_frame_out)) != PVX_OK) return rc;
     const HostOut o = block_ptrs(p->d_wiretmp, rows, p->npks);
-    rc = analyze_rows(p, d_x, x_dtype, nsamp, nsig, sig_stride, F, o.f, o.mag, o.ph, o.realph, o.binno, nullptr, o.totalmag, nullptr, (hipStream_t)stream);
+    rc = analyze_rows(p, route, d_x, x_dtype, nsamp, nsig, sig_stride, F, o.f, o.mag, o.ph, o.realph, o.binno, nullptr, o.totalmag, nullptr, (hipStream_t)stream);
     if (rc != PVX_OK) return rc;
     rc = pvx_pack_rows_dev(p, rows, o.f, o.mag, o.ph, o.binno, o.totalmag, d_wire, stream);
     return rc == PVX_OK ? F : rc;
