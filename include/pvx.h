@@ -403,6 +403,32 @@ int64_t pvx_periodicity_dev(const double* d_x, int64_t nsamp, const double* wind
                             double* d_cand_period, double* d_cand_strength, int32_t* d_ncands,
                             int32_t* d_preferred, void* stream);
 
+/* ---- FFT filter banks: FilterBank.specout, MelFilterBank.mfcc (pypevoc/FFTFilters.py:274-292, 352-374) ----
+ *
+ * pvx_filterbank: frames start at i*hop while i*hop < n - nwind (:280; n <= nwind: no frame).  Per frame
+ *   spec[i][b] = sum_k |fft(x[i*hop : i*hop+nwind] * wind)[k]|^2 * fb[b][k]        (:283-286)
+ * with fb [nband][nwind] the reference's weights over the FULL spectrum (host array, read at call time, any shape of
+ * row, all-zero rows included) and wind the bare window (no 1/wfact).  cep_mode != 0 also gives the cepstral step on
+ * log(spec[i]) (no floor: log(0) = -inf): PVX_CEP_DCT1 .. PVX_CEP_DCT4 = scipy.fftpack.dct(type, norm=None) into
+ * cep [nfr][nband]; PVX_CEP_IFFT = np.fft.ifft into cep [nfr][nband][2] (re, im).  A frame whose band energies are all 0
+ * gets the reference's row for it ([-inf, nan, ...] DCT1 / DCT2, all nan DCT3 / DCT4, [-inf+0j, nan+nanj, ...] IFFT).
+ * x: float32, float64 or int16 samples (pvx_dtype), widened on load; all arithmetic float64.  spec or cep may be NULL.
+ * nwind 512 / 1024 / 2048 run one fused kernel per call, any other nwind (odd ones too) k_frames + rocFFT + one kernel
+ * per batch of rows.  1 <= nband <= PVX_FBANK_MAX_NBAND, else PVX_ERR_UNSUPPORTED.  Host input is chunked by
+ * PVX_MAX_DEVICE_BYTES (frames are independent: device memory does not grow with n).
+ * pvx_filterbank_dev: x, spec and cep are device memory (wind and fb stay host arrays), work on `stream`, synchronised
+ * before the return.  Both return the frame count or a negative status.  Calls share a per-device workspace kept for the
+ * process and take turns on it.  pvx_filterbank_last_kernels: the kernels the calling thread's last call ran
+ * ("k_fbank_fused<1024>", "k_frames+rocfft+k_fbank_rows"; "" when it had no frame).
+ */
+#define PVX_FBANK_MAX_NBAND 128
+typedef enum { PVX_CEP_NONE = 0, PVX_CEP_DCT1 = 1, PVX_CEP_DCT2 = 2, PVX_CEP_DCT3 = 3, PVX_CEP_DCT4 = 4, PVX_CEP_IFFT = 5 } pvx_cep_mode;
+int64_t pvx_filterbank(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, const double* fb,
+                       int nband, int cep_mode, double* spec, double* cep);
+int64_t pvx_filterbank_dev(const void* d_x, int x_dtype, int64_t n, const double* wind, int nwind, int hop,
+                           const double* fb, int nband, int cep_mode, double* d_spec, double* d_cep, void* stream);
+const char* pvx_filterbank_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

@@ -12,7 +12,10 @@ from .PeakFinder import PeakFinder  # noqa: F401
 from .batch import PVBatch, PVMany  # noqa: F401
 from .Periodicity import (PeriodSeries, PeriodTimeSeries, period_marks_corr,  # noqa: F401  (pypevoc/__init__.py:2)
                           period_marks_peak, period_marks_amdf)
+from .FFTFilters import FilterBank, TriangularFilterBank, MelFilterBank, PiecewiseFilterSpec  # noqa: F401
+from . import FFTFilters  # noqa: F401  (`from pypevoc_amd import FFTFilters as ft`, as the reference's examples import it)
 from ._lib import PvxError  # noqa: F401
 
 __all__ = ["PV", "PVHarmonic", "SinSum", "RegPartial", "PeakFinder", "PVBatch", "PVMany", "PvxError",
-           "PeriodSeries", "PeriodTimeSeries", "period_marks_corr", "period_marks_peak", "period_marks_amdf"]
+           "PeriodSeries", "PeriodTimeSeries", "period_marks_corr", "period_marks_peak", "period_marks_amdf",
+           "FilterBank", "TriangularFilterBank", "MelFilterBank", "PiecewiseFilterSpec", "FFTFilters"]

@@ -124,6 +124,11 @@ SIGNATURES = {
     "pvx_periodicity_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int, c_int64_p, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                              ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 5),
+    "pvx_filterbank": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
+                                        ctypes.c_int, ctypes.c_int, c_double_p, c_double_p]),
+    "pvx_filterbank_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvx_filterbank_last_kernels": (ctypes.c_char_p, []),
 }
 
 

@@ -2236,6 +2236,68 @@ extern "C" int64_t pvx_periodicity(const double* x, int64_t nsamp, const double*
     return nidx;
 }
 
+// ---- FFT filter banks (k_fbank.hip) -----------------------------------------------------------
+static thread_local const char* t_fbank_kernels = "";
+extern "C" const char* pvx_filterbank_last_kernels(void) { return t_fbank_kernels; }
+
+static int fbank_args(int x_dtype, int64_t n, const double* wind, int nwind, int hop, const double* fb, int nband, int cep_mode,
+                      const double* spec, const double* cep) {
+    if (n < 0 || !wind || nwind < 2 || hop < 1 || !fb || nband < 1) { pvx_set_error("bad filter-bank argument"); return PVX_ERR_INVALID; }
+    if (x_dtype != PVX_F32 && x_dtype != PVX_F64 && x_dtype != PVX_I16) { pvx_set_error("bad x_dtype %d", x_dtype); return PVX_ERR_INVALID; }
+    if (cep_mode < PVX_CEP_NONE || cep_mode > PVX_CEP_IFFT) { pvx_set_error("pvx_filterbank: unknown cep_mode %d", cep_mode); return PVX_ERR_INVALID; }
+    if (nband > PVX_FBANK_MAX_NBAND) { pvx_set_error("pvx_filterbank: %d bands (the kernels take up to %d)", nband, PVX_FBANK_MAX_NBAND); return PVX_ERR_UNSUPPORTED; }
+    if (cep_mode == PVX_CEP_DCT1 && nband < 2) { pvx_set_error("pvx_filterbank: DCT type 1 needs at least 2 bands"); return PVX_ERR_INVALID; }
+    if ((cep_mode != PVX_CEP_NONE && !cep) || (!spec && !cep)) { pvx_set_error("null filter-bank output"); return PVX_ERR_INVALID; }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_filterbank_dev(const void* d_x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, const double* fb,
+                                      int nband, int cep_mode, double* d_spec, double* d_cep, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = fbank_args(x_dtype, n, wind, nwind, hop, fb, nband, cep_mode, d_spec, d_cep)) != PVX_OK) return rc;
+    t_fbank_kernels = "";
+    const int64_t nfr = pvx_nframes(n, nwind, hop);                   // FFTFilters.py:280: n < len(w) - nwind, the analysis framing
+    if (nfr == 0) return 0;
+    if (!d_x) { pvx_set_error("null filter-bank signal"); return PVX_ERR_INVALID; }
+    if ((rc = pvx_fbank_run(d_x, x_dtype, nfr, wind, nwind, hop, fb, nband, cep_mode, d_spec, cep_mode ? d_cep : nullptr,
+                            (hipStream_t)stream, &t_fbank_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nfr;
+}
+
+extern "C" int64_t pvx_filterbank(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, const double* fb,
+                                  int nband, int cep_mode, double* spec, double* cep) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = fbank_args(x_dtype, n, wind, nwind, hop, fb, nband, cep_mode, spec, cep)) != PVX_OK) return rc;
+    t_fbank_kernels = "";
+    const int64_t nfr = pvx_nframes(n, nwind, hop);
+    if (nfr == 0) return 0;
+    if (!x) { pvx_set_error("null filter-bank signal"); return PVX_ERR_INVALID; }
+    if (!cep_mode) cep = nullptr;
+    // frames do not depend on each other: a chunk of frames needs its own samples only (neighbouring chunks overlap by
+    // nwind - hop), so the device holds one chunk of input and its results whatever the signal's length
+    size_t limit = (size_t)2 << 30;                                   // per buffer
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
+    const size_t es = dtype_size(x_dtype);
+    const size_t sb = (size_t)nband * 8, cb = cep ? sb * (cep_mode == PVX_CEP_IFFT ? 2 : 1) : 0;
+    int64_t fc = (int64_t)(limit / es) > nwind ? ((int64_t)(limit / es) - nwind) / hop + 1 : 1;
+    fc = std::min<int64_t>(fc, std::max<int64_t>(1, (int64_t)(limit / std::max(sb, cb))));
+    fc = std::min(fc, nfr);
+    DevBuf dx, ds, dc;
+    if ((rc = dx.alloc((size_t)((fc - 1) * hop + nwind) * es)) != PVX_OK || (spec && (rc = ds.alloc((size_t)fc * sb)) != PVX_OK) ||
+        (cep && (rc = dc.alloc((size_t)fc * cb)) != PVX_OK)) return rc;
+    for (int64_t f0 = 0; f0 < nfr; f0 += fc) {
+        const int64_t cnt = std::min(fc, nfr - f0);
+        if ((rc = host_to_device(dx.p, (const char*)x + (size_t)(f0 * hop) * es, (size_t)((cnt - 1) * hop + nwind) * es)) != PVX_OK) return rc;
+        if ((rc = pvx_fbank_run(dx.p, x_dtype, cnt, wind, nwind, hop, fb, nband, cep_mode, spec ? (double*)ds.p : nullptr,
+                                cep ? (double*)dc.p : nullptr, nullptr, &t_fbank_kernels)) != PVX_OK) return rc;
+        if (spec && (rc = device_to_host((char*)spec + (size_t)f0 * sb, ds.p, (size_t)cnt * sb)) != PVX_OK) return rc;
+        if (cep && (rc = device_to_host((char*)cep + (size_t)f0 * cb, dc.p, (size_t)cnt * cb)) != PVX_OK) return rc;
+    }
+    return nfr;
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

@@ -297,6 +297,12 @@ struct PeriodParams {
 // workspace the calls share, one at a time)
 int pvx_period_run(PeriodParams p, const double* h_wind, const int64_t* h_idx, hipStream_t s);
 
+// FFT filter banks (k_fbank.hip, FFTFilters.py:274-292, 352-374): band energies and cepstra of frames 0 .. nfr of the device
+// signal d_x (frame i starts at i * hop).  The window, fb [nband][nwind] (full spectrum) are host arrays; d_spec / d_cep device
+// memory (either may be null).  Synchronises the stream; *kernels names what ran.
+int pvx_fbank_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_wind, int nwind, int hop, const double* h_fb, int nband,
+                  int cep_mode, double* d_spec, double* d_cep, hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)
