@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pvx_internal.h"
+#include "pvx_mem.h"
 #include "pvx_stft.h"
 #include "pvx_wave.h"
 
@@ -270,37 +271,21 @@ template <int R> int launch_fused(const FbankParams& p, int x_dtype, hipStream_t
 // ---- per-device workspace: tables of the call, the rows route's buffers and rocFFT plans.  Kept for the process, grow-only,
 // held for a whole call (execution and the final synchronisation included): callers on one device take turns.
 struct FftPlan {
-    rocfft_plan plan = nullptr;
-    rocfft_execution_info info = nullptr;
+    RealFft fft;
     int64_t batch = 0;
 };
 struct FbankWs {
     std::mutex mu;
     std::vector<double> h_tab;                                        // host image of `tab` (alive until the call's copy is done)
     std::vector<int> h_band;
-    void *tab = nullptr, *band = nullptr, *frames = nullptr, *spec = nullptr, *work = nullptr;
-    size_t tab_cap = 0, band_cap = 0, frames_cap = 0, spec_cap = 0, work_cap = 0;
+    DevMem tab, band, frames, spec;                                   // (exactly as large as the largest request so far)
+    DevMem work;                                                      // the one rocFFT work buffer the plans share
     std::map<int, FftPlan> plans;                                     // nwind -> plan of the rows route
 };
 std::mutex g_ws_mu;
 std::map<int, FbankWs*> g_ws;                                         // device -> workspace (never erased)
 constexpr size_t kMaxPlans = 4;                                       // window lengths with a live rocFFT plan
 
-int grow(void** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return PVX_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }           // (no work is pending: every call ends synchronised)
-    if (hipMalloc(p, need ? need : 1) != hipSuccess) { *p = nullptr; pvx_set_error("hipMalloc(%zu) failed", need); return PVX_ERR_ALLOC; }
-    *cap = need;
-    return PVX_OK;
-}
-
-void release_plans(FbankWs& w) {
-    for (auto& kv : w.plans) {
-        if (kv.second.info) (void)rocfft_execution_info_destroy(kv.second.info);
-        if (kv.second.plan) (void)rocfft_plan_destroy(kv.second.plan);
-    }
-    w.plans.clear();
-}
 
 // rows per rocFFT batch: the windowed frames of a batch stay near 32 MB (and the half-spectrum rows beside them).  Fixed per
 // nwind, whatever the call's frame count: a row's spectrum does not depend on how many rows the call has
@@ -312,47 +297,30 @@ int64_t rows_batch(int nwind) {
 int ensure_plan(FbankWs& w, int nwind, FftPlan** out) {
     auto it = w.plans.find(nwind);
     if (it != w.plans.end()) { *out = &it->second; return PVX_OK; }
-    if (w.plans.size() >= kMaxPlans) release_plans(w);
+    if (w.plans.size() >= kMaxPlans) w.plans.clear();
     FftPlan fp;
     fp.batch = rows_batch(nwind);
-    rocfft_plan_description desc = nullptr;
-    PVX_FFT_CHECK(rocfft_plan_description_create(&desc));
-    size_t istride = 1, ostride = 1;
-    rocfft_status st = rocfft_plan_description_set_data_layout(desc, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                               nullptr, 1, &istride, (size_t)nwind, 1, &ostride, (size_t)(nwind / 2 + 1));
-    size_t len = (size_t)nwind;
-    if (st == rocfft_status_success)
-        st = rocfft_plan_create(&fp.plan, rocfft_placement_notinplace, rocfft_transform_type_real_forward, rocfft_precision_double, 1, &len,
-                                (size_t)fp.batch, desc);
-    rocfft_plan_description_destroy(desc);
-    if (st != rocfft_status_success) {
-        pvx_set_error("rocfft_plan_create(nwind=%d, batch=%lld) failed: %d", nwind, (long long)fp.batch, (int)st);
-        return PVX_ERR_HIP;
+    rocfft_status st;
+    switch (fp.fft.create((size_t)nwind, (size_t)fp.batch, rocfft_precision_double, rocfft_placement_notinplace, (size_t)nwind, (size_t)(nwind / 2 + 1), &st)) {
+        case RealFft::done: break;
+        case RealFft::describe: pvx_set_error("rocfft_plan_description_create failed: rocfft_status %d", (int)st); return PVX_ERR_HIP;
+        case RealFft::plan: pvx_set_error("rocfft_plan_create(nwind=%d, batch=%lld) failed: %d", nwind, (long long)fp.batch, (int)st); return PVX_ERR_HIP;
+        case RealFft::info: pvx_set_error("rocfft execution setup (nwind=%d) failed", nwind); return PVX_ERR_HIP;
     }
-    size_t wb = 0;
-    if (rocfft_plan_get_work_buffer_size(fp.plan, &wb) != rocfft_status_success || rocfft_execution_info_create(&fp.info) != rocfft_status_success) {
-        (void)rocfft_plan_destroy(fp.plan);
-        pvx_set_error("rocfft execution setup (nwind=%d) failed", nwind);
-        return PVX_ERR_HIP;
+    const size_t wb = fp.fft.work_bytes();
+    if (wb > w.work.cap()) {
+        // the plans share one work buffer (calls take turns); a larger one invalidates what the other plans were told: the old
+        // one goes only once the new one exists, and every live plan hears of it
+        DevMem larger;
+        if (larger.alloc(wb) != PVX_OK) { pvx_set_error("hipMalloc(rocfft work, %zu) failed", wb); return PVX_ERR_ALLOC; }
+        w.work = std::move(larger);
+        for (auto& kv : w.plans) (void)kv.second.fft.set_work(w.work.get(), w.work.cap());
     }
-    if (wb > w.work_cap) {
-        // the plans share one work buffer (calls take turns); a larger one invalidates what the other plans were told
-        void* nwk = nullptr;
-        if (hipMalloc(&nwk, wb) != hipSuccess) {
-            (void)rocfft_execution_info_destroy(fp.info); (void)rocfft_plan_destroy(fp.plan);
-            pvx_set_error("hipMalloc(rocfft work, %zu) failed", wb);
-            return PVX_ERR_ALLOC;
-        }
-        if (w.work) (void)hipFree(w.work);
-        w.work = nwk; w.work_cap = wb;
-        for (auto& kv : w.plans) (void)rocfft_execution_info_set_work_buffer(kv.second.info, w.work, w.work_cap);
-    }
-    if (w.work && rocfft_execution_info_set_work_buffer(fp.info, w.work, w.work_cap) != rocfft_status_success) {
-        (void)rocfft_execution_info_destroy(fp.info); (void)rocfft_plan_destroy(fp.plan);
+    if (w.work && fp.fft.set_work(w.work.get(), w.work.cap()) != rocfft_status_success) {
         pvx_set_error("rocfft set_work_buffer failed");
         return PVX_ERR_HIP;
     }
-    *out = &(w.plans[nwind] = fp);
+    *out = &(w.plans[nwind] = std::move(fp));
     return PVX_OK;
 }
 
@@ -439,14 +407,14 @@ int run_locked(FbankWs& w, const void* d_x, int x_dtype, int64_t nfr, const doub
         silent_row(cep_mode, nband, &t[off_sil]);
     }
     int rc;
-    if ((rc = grow(&w.tab, &w.tab_cap, t.size() * 8)) != PVX_OK || (rc = grow(&w.band, &w.band_cap, hb.size() * 4)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipMemcpyAsync(w.tab, t.data(), t.size() * 8, hipMemcpyHostToDevice, s));
-    PVX_HIP_CHECK(hipMemcpyAsync(w.band, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
-    const double* dt = (const double*)w.tab;
+    if ((rc = w.tab.grow(t.size() * 8, Sizing::exact)) != PVX_OK || (rc = w.band.grow(hb.size() * 4, Sizing::exact)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemcpyAsync(w.tab.get(), t.data(), t.size() * 8, hipMemcpyHostToDevice, s));
+    PVX_HIP_CHECK(hipMemcpyAsync(w.band.get(), hb.data(), hb.size() * 4, hipMemcpyHostToDevice, s));
+    const double* dt = w.tab.as<const double>();
     FbankParams p = {};
     p.hop = hop; p.nband = nband; p.cep_mode = cep_mode;
     p.win = dt; p.twiddle = dt + off_tw;
-    p.band_lo = (const int*)w.band; p.band_n = p.band_lo + nband; p.band_off = p.band_lo + 2 * nband;
+    p.band_lo = w.band.as<const int>(); p.band_n = p.band_lo + nband; p.band_off = p.band_lo + 2 * nband;
     p.wf = dt + off_wf; p.cre = dt + off_cre; p.cim = dt + off_cim; p.silent = dt + off_sil;
     const int cpx = cep_mode == 5 ? 2 : 1;
     if (fused) {
@@ -461,19 +429,17 @@ int run_locked(FbankWs& w, const void* d_x, int x_dtype, int64_t nfr, const doub
         FftPlan* fp = nullptr;
         if ((rc = ensure_plan(w, nwind, &fp)) != PVX_OK) return rc;
         const int64_t batch = fp->batch;
-        if ((rc = grow(&w.frames, &w.frames_cap, (size_t)batch * nwind * 8)) != PVX_OK ||
-            (rc = grow(&w.spec, &w.spec_cap, (size_t)batch * nhalf * 16)) != PVX_OK) return rc;
-        PVX_FFT_CHECK(rocfft_execution_info_set_stream(fp->info, s));
+        if ((rc = w.frames.grow((size_t)batch * nwind * 8, Sizing::exact)) != PVX_OK ||
+            (rc = w.spec.grow((size_t)batch * nhalf * 16, Sizing::exact)) != PVX_OK) return rc;
         for (int64_t c0 = 0; c0 < nfr; c0 += batch) {
             const int64_t rows = nfr - c0 < batch ? nfr - c0 : batch;
             // workspace row j = frame c0 + j in k_frames' row space (pvx_internal.h: global row g holds frame g - 1)
             FrameParams fr = {};
             fr.x = d_x; fr.nsamp = 0; fr.sig_stride = 0; fr.F = nfr; fr.R0 = c0 + 2; fr.ws_rows = rows; fr.total_rows = nfr + 1;
-            fr.nfft = nwind; fr.hop = hop; fr.win = dt; fr.frames = w.frames; fr.ldi = nwind;
+            fr.nfft = nwind; fr.hop = hop; fr.win = dt; fr.frames = w.frames.get(); fr.ldi = nwind;
             if ((rc = pvx_launch_frames(fr, x_dtype, 64, s)) != PVX_OK) return rc;
-            void* in[1] = {w.frames}, *out[1] = {w.spec};
-            PVX_FFT_CHECK(rocfft_execute(fp->plan, in, out, fp->info));   // the whole batch: rows beyond `rows` are not read
-            p.rows = w.spec; p.ldo = nhalf; p.nfr = rows;
+            PVX_FFT_CHECK(fp->fft.execute(w.frames.get(), w.spec.get(), s));   // the whole batch: rows beyond `rows` are not read
+            p.rows = w.spec.get(); p.ldo = nhalf; p.nfr = rows;
             p.spec = d_spec ? d_spec + c0 * nband : nullptr;
             p.cep = d_cep ? d_cep + c0 * (int64_t)(nband * cpx) : nullptr;
             hipLaunchKernelGGL(k_fbank_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, p);

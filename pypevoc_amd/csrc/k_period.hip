@@ -23,6 +23,7 @@
 #include <tuple>
 
 #include "pvx_internal.h"
+#include "pvx_mem.h"
 
 namespace {
 
@@ -360,29 +361,13 @@ struct PeriodWs {
     std::mutex mu;
     int fft_nwind = 0;
     int64_t fft_batch = 0;
-    rocfft_plan plan = nullptr;
-    rocfft_execution_info info = nullptr;
-    void* work = nullptr;
-    size_t work_cap = 0;
-    void *wind = nullptr, *wnorm = nullptr, *idx = nullptr, *scratch = nullptr, *frames = nullptr, *spec = nullptr, *err = nullptr;
-    size_t wind_cap = 0, wnorm_cap = 0, idx_cap = 0, scratch_cap = 0, frames_cap = 0, spec_cap = 0, err_cap = 0;
+    RealFft fft;
+    DevMem work;                                                     // rocFFT's work buffer: kept when a new nwind replaces the plan
+    DevMem wind, wnorm, idx, scratch, frames, spec, err;
 };
 std::mutex g_ws_mu;
 std::map<int, PeriodWs*> g_ws;                                       // device -> workspace (never erased)
 
-int grow(void** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return PVX_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }           // (no work is pending: every call ends synchronised)
-    if (hipMalloc(p, need ? need : 1) != hipSuccess) { *p = nullptr; pvx_set_error("hipMalloc(%zu) failed", need); return PVX_ERR_ALLOC; }
-    *cap = need;
-    return PVX_OK;
-}
-
-void release_fft(PeriodWs& w) {
-    if (w.info) (void)rocfft_execution_info_destroy(w.info);
-    if (w.plan) (void)rocfft_plan_destroy(w.plan);
-    w.info = nullptr; w.plan = nullptr; w.fft_nwind = 0; w.fft_batch = 0;
-}
 
 // frames per 'fft' chunk: the rocFFT input / output of a chunk stay near 64 MB each
 int64_t fft_chunk(int nwind) {
@@ -390,37 +375,24 @@ int64_t fft_chunk(int nwind) {
     return c < 1 ? 1 : c;
 }
 
+// (the buffers are exactly as large as the largest request so far; no work is pending when one is replaced: every call ends
+// synchronised)
 int ensure_fft(PeriodWs& w, int nwind) {
-    if (w.plan && w.fft_nwind == nwind) return PVX_OK;
-    release_fft(w);
+    if (w.fft && w.fft_nwind == nwind) return PVX_OK;
+    w.fft_nwind = 0; w.fft_batch = 0;
     const int64_t batch = fft_chunk(nwind);
-    rocfft_plan_description desc = nullptr;
-    PVX_FFT_CHECK(rocfft_plan_description_create(&desc));
-    size_t istride = 1, ostride = 1;
-    rocfft_status st = rocfft_plan_description_set_data_layout(desc, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr,
-                                                               nullptr, 1, &istride, (size_t)nwind, 1, &ostride, (size_t)(nwind / 2 + 1));
-    size_t len = (size_t)nwind;
-    if (st == rocfft_status_success)
-        st = rocfft_plan_create(&w.plan, rocfft_placement_notinplace, rocfft_transform_type_real_forward, rocfft_precision_double, 1, &len,
-                                (size_t)batch, desc);
-    rocfft_plan_description_destroy(desc);
-    if (st != rocfft_status_success) {
-        w.plan = nullptr;
-        pvx_set_error("rocfft_plan_create(nwind=%d, batch=%lld) failed: %d", nwind, (long long)batch, (int)st);
-        return PVX_ERR_HIP;
+    rocfft_status st;
+    switch (w.fft.create((size_t)nwind, (size_t)batch, rocfft_precision_double, rocfft_placement_notinplace, (size_t)nwind, (size_t)(nwind / 2 + 1), &st)) {
+        case RealFft::done: break;
+        case RealFft::describe: pvx_set_error("rocfft_plan_description_create failed: rocfft_status %d", (int)st); return PVX_ERR_HIP;
+        case RealFft::plan: pvx_set_error("rocfft_plan_create(nwind=%d, batch=%lld) failed: %d", nwind, (long long)batch, (int)st); return PVX_ERR_HIP;
+        case RealFft::info: pvx_set_error("rocfft execution setup (nwind=%d) failed", nwind); return PVX_ERR_HIP;
     }
-    size_t wb = 0;
-    int rc;
-    if (rocfft_plan_get_work_buffer_size(w.plan, &wb) != rocfft_status_success || rocfft_execution_info_create(&w.info) != rocfft_status_success) {
-        w.info = nullptr;
-        release_fft(w);
-        pvx_set_error("rocfft execution setup (nwind=%d) failed", nwind);
-        return PVX_ERR_HIP;
-    }
-    if (wb) {
-        if ((rc = grow(&w.work, &w.work_cap, wb)) != PVX_OK) { release_fft(w); return rc; }
-        if (rocfft_execution_info_set_work_buffer(w.info, w.work, wb) != rocfft_status_success) {
-            release_fft(w);
+    if (const size_t wb = w.fft.work_bytes()) {
+        int rc;
+        if ((rc = w.work.grow(wb, Sizing::exact)) != PVX_OK) { w.fft.reset(); return rc; }
+        if (w.fft.set_work(w.work.get(), wb) != rocfft_status_success) {
+            w.fft.reset();
             pvx_set_error("rocfft set_work_buffer failed");
             return PVX_ERR_HIP;
         }
@@ -435,34 +407,34 @@ int run_locked(PeriodWs& w, PeriodParams p, const double* h_wind, const int64_t*
     const bool inlds = n <= kLdsMax;
     const bool fft = p.cand_method == PVX_CAND_FFT;
     int rc;
-    if ((rc = grow(&w.wind, &w.wind_cap, (size_t)n * 8)) != PVX_OK || (rc = grow(&w.idx, &w.idx_cap, (size_t)p.nfr * 8)) != PVX_OK ||
-        (rc = grow(&w.err, &w.err_cap, 4)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipMemcpyAsync(w.wind, h_wind, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    PVX_HIP_CHECK(hipMemcpyAsync(w.idx, h_idx, (size_t)p.nfr * 8, hipMemcpyHostToDevice, s));
-    PVX_HIP_CHECK(hipMemsetAsync(w.err, 0, 4, s));
-    p.wind = (const double*)w.wind;
-    p.idx = (const int64_t*)w.idx;
-    p.err = (int*)w.err;
+    if ((rc = w.wind.grow((size_t)n * 8, Sizing::exact)) != PVX_OK || (rc = w.idx.grow((size_t)p.nfr * 8, Sizing::exact)) != PVX_OK ||
+        (rc = w.err.grow(4, Sizing::exact)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemcpyAsync(w.wind.get(), h_wind, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    PVX_HIP_CHECK(hipMemcpyAsync(w.idx.get(), h_idx, (size_t)p.nfr * 8, hipMemcpyHostToDevice, s));
+    PVX_HIP_CHECK(hipMemsetAsync(w.err.get(), 0, 4, s));
+    p.wind = w.wind.as<const double>();
+    p.idx = w.idx.as<const int64_t>();
+    p.err = w.err.as<int>();
     if (!p.amdf) {
-        if ((rc = grow(&w.wnorm, &w.wnorm_cap, (size_t)n * 8)) != PVX_OK) return rc;
-        hipLaunchKernelGGL(k_window_acf, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, p.wind, n, (double*)w.wnorm);
+        if ((rc = w.wnorm.grow((size_t)n * 8, Sizing::exact)) != PVX_OK) return rc;
+        hipLaunchKernelGGL(k_window_acf, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, p.wind, n, w.wnorm.as<double>());
         PVX_HIP_CHECK(hipGetLastError());
-        p.wnorm = (const double*)w.wnorm;
+        p.wnorm = w.wnorm.as<const double>();
     }
     int64_t chunk = p.nfr;
     if (fft) {
         if ((rc = ensure_fft(w, n)) != PVX_OK) return rc;
         chunk = w.fft_batch < p.nfr ? w.fft_batch : p.nfr;
         // the plan transforms fft_batch rows: rows beyond a call's frames hold zeros or an earlier call's frames, never read
-        const bool fresh = w.frames_cap < (size_t)w.fft_batch * n * 8;
-        if ((rc = grow(&w.frames, &w.frames_cap, (size_t)w.fft_batch * n * 8)) != PVX_OK ||
-            (rc = grow(&w.spec, &w.spec_cap, (size_t)w.fft_batch * (n / 2 + 1) * 16)) != PVX_OK) return rc;
-        if (fresh) PVX_HIP_CHECK(hipMemsetAsync(w.frames, 0, w.frames_cap, s));
+        const bool fresh = w.frames.cap() < (size_t)w.fft_batch * n * 8;
+        if ((rc = w.frames.grow((size_t)w.fft_batch * n * 8, Sizing::exact)) != PVX_OK ||
+            (rc = w.spec.grow((size_t)w.fft_batch * (n / 2 + 1) * 16, Sizing::exact)) != PVX_OK) return rc;
+        if (fresh) PVX_HIP_CHECK(hipMemsetAsync(w.frames.get(), 0, w.frames.cap(), s));
     }
     const int64_t gmax = inlds ? 1024 : 512;
     const int64_t grid = chunk < gmax ? chunk : gmax;
-    if ((rc = grow(&w.scratch, &w.scratch_cap, (size_t)grid * (size_t)(inlds ? n : 2 * n + kR) * 8)) != PVX_OK) return rc;
-    p.scratch = (double*)w.scratch;
+    if ((rc = w.scratch.grow((size_t)grid * (size_t)(inlds ? n : 2 * n + kR) * 8, Sizing::exact)) != PVX_OK) return rc;
+    p.scratch = w.scratch.as<double>();
     const size_t lds = inlds ? (size_t)n * 8 : 0;
     PeriodParams q = p;
     for (int64_t f0 = 0; f0 < p.nfr; f0 += chunk) {
@@ -474,7 +446,7 @@ int run_locked(PeriodWs& w, PeriodParams p, const double* h_wind, const int64_t*
         q.cand_strength = p.cand_strength + f0 * p.ncand;
         q.ncands = p.ncands + f0;
         q.preferred = p.preferred + f0;
-        q.xw_out = fft ? (double*)w.frames : nullptr;
+        q.xw_out = fft ? w.frames.as<double>() : nullptr;
         const unsigned g = (unsigned)(nf < grid ? nf : grid);
         if (p.amdf) {
             if (inlds) hipLaunchKernelGGL((k_period<true, true>), dim3(g), dim3(kThreads), lds, s, q);
@@ -485,16 +457,13 @@ int run_locked(PeriodWs& w, PeriodParams p, const double* h_wind, const int64_t*
         }
         PVX_HIP_CHECK(hipGetLastError());
         if (fft) {
-            void* in[1] = {w.frames};
-            void* out[1] = {w.spec};
-            PVX_FFT_CHECK(rocfft_execution_info_set_stream(w.info, s));
-            PVX_FFT_CHECK(rocfft_execute(w.plan, in, out, w.info));
-            hipLaunchKernelGGL(k_period_fft, dim3(g), dim3(kThreads), 0, s, q, (const double2*)w.spec, nf);
+            PVX_FFT_CHECK(w.fft.execute(w.frames.get(), w.spec.get(), s));
+            hipLaunchKernelGGL(k_period_fft, dim3(g), dim3(kThreads), 0, s, q, w.spec.as<const double2>(), nf);
             PVX_HIP_CHECK(hipGetLastError());
         }
     }
     int herr = 0;
-    PVX_HIP_CHECK(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, s));
+    PVX_HIP_CHECK(hipMemcpyAsync(&herr, w.err.get(), 4, hipMemcpyDeviceToHost, s));
     PVX_HIP_CHECK(hipStreamSynchronize(s));                          // the workspace is free for the next call from here on
     if (herr & 1) { pvx_set_error("pvx_periodicity: a frame centre leaves the signal"); return PVX_ERR_INVALID; }
     if (herr & 2) {

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <mutex>
 #include <thread>
@@ -21,6 +22,7 @@
 #include <time.h>
 
 #include "pvx_internal.h"
+#include "pvx_mem.h"
 
 // float64 -> float32 while staging (RNE, what v_cvt_f32_f64 does on the device): AVX2 where the host has it
 #if defined(__x86_64__)
@@ -171,87 +173,81 @@ struct pvx_plan {
     int64_t ldi = 0, ldo = 0; // workspace row pitches (elements / complex elements)
     std::vector<double> win;  // caller's window
     bool win_symmetric = false;  // win[n] == win[nfft-1-n] for every n
-    void* d_win = nullptr;    // window / wfact in the working precision
-    double* d_wfbin = nullptr;
-    void* d_frames = nullptr; // [max_rows+1][ldi]
-    void* d_spec = nullptr;   // [max_rows+1][ldo] complex
-    void* d_cand_y = nullptr;              // the split transform's candidate peaks per workspace row (pvx_stft.h): |X|^2 [max_rows+1][cand_cap],
-    unsigned short* d_cand_bin = nullptr;  // bins, and [max_rows+1][4] max / min / sum / count
-    double* d_cand_stats = nullptr;
-    int cand_cap = 0;
-    void* d_work = nullptr;
-    size_t work_bytes = 0;
+    int cand_cap = 0;            // entries per row of d_cand_y / d_cand_bin
     int64_t ws_bytes = 0;
-    rocfft_plan fft = nullptr;
-    rocfft_execution_info info = nullptr;
     bool rocfft_ready = false;   // frames/spectrum workspace + rocFFT plan are created on first use
-    double* d_lastspec = nullptr;   // k_pv_rev / k_pv_team: [N2][2] the spectrum of the one row a call asks for (chunk carry, last_spec)
-    void* d_pvstage = nullptr;   // k_pv_rev at nfft 2048: the kept peaks' values between the frames (PvRevParams::stage)
-    size_t pvstage_cap = 0;
     int wire_fmt = 1;            // the gather's wire format (k_wire.hip): 1 = f as float64, 2 = the float32 it is computed from (pvx_plan_set_wire_format)
-    double* d_wiretmp = nullptr; // pvx_analyze_dev_wire on plans whose kernels do not write the wire format themselves: the result block that is then packed
-    size_t wiretmp_cap = 0;
     int64_t rocfft_rows = 0;     // rows of the rocFFT workspace (2 when only pvx_stft_frames uses it)
     bool rocfft_small = false;   // ... and its output then goes to d_rspec, not to the analysis' d_spec
-    void* d_rspec = nullptr;     // rocFFT output when the main spectrum workspace belongs to k_stft
-    void* d_twiddle64 = nullptr; // complex<T>[nfft] W_nfft^j for k_stft (T = the plan's precision)
-    void* d_twiddle = nullptr;   // float2[2048] W_2048^j for the fused kernel
-    float* d_specrow = nullptr;  // 1024 complex: spectrum of one requested row (fused mode)
-    // PVHarmonic: per-frame f0 / previous-row tables and the carried spectrum of the last valid frame
-    double* d_hf0 = nullptr;
-    unsigned char* d_hx = nullptr;         // pvx_harmonic_analyze: the host signal's device copy (kept: allocating and freeing
-    size_t hx_cap = 0;                     // hundreds of MB per call cost more than the analysis)
-    int32_t* d_hprev = nullptr;
-    void* d_carry = nullptr;
-    int64_t harm_cap = 0;
+    int64_t harm_cap = 0;        // entries of d_hf0 / d_hprev
     // progress callback of the host entry points
     pvx_progress_fn progress_fn = nullptr;
     void* progress_user = nullptr;
     bool progress_live = false;   // inside a host entry point: chunk completions are reported
     int64_t fused_blocks = 0;    // PVX_FUSED_BLOCKS override
     int frames_per_wave = 2;     // k_phase_peaks: frames a wave handles one after the other (latency floor of a chunked launch; PVX_FPW)
-    // ---- host entry points: plan-owned, grow-only buffers (no hipMalloc / hipFree per call)
-    hipStream_t s_host = nullptr;          // non-blocking stream of the host entry points
-    hipStream_t s_copy = nullptr;          // second stream: DMA of finished waveform slices under the next slice's kernel
-    hipEvent_t ev_done[2] = {nullptr, nullptr};
-    void* d_in[2] = {nullptr, nullptr};    // input chunks (double-buffered: H2D of chunk i+1 under the kernels of chunk i)
-    size_t in_cap[2] = {0, 0};
-    double* d_out[2] = {nullptr, nullptr}; // result blocks of a chunk when the results stream back to the host
-    size_t out_cap[2] = {0, 0};
-    void* h_pin = nullptr;                 // pinned staging of small calls (input, then the result block)
-    size_t pin_cap = 0;
-    void* h_ring = nullptr;                // pinned ring of the threaded staging of large host transfers (kStageThreads x 2 slots)
-    hipEvent_t ev_ring[16] = {};
-    double* d_prev = nullptr;              // [N2][2] spectrum carried from one input chunk to the next (PV.py:209)
     // resident results (pvx_analyze_resident): the reference's arrays stay in HBM for the tracker, the
     // resynthesis and the frame descriptors; only what the caller fetches crosses PCIe
-    double* d_res = nullptr;
-    size_t res_cap = 0;
     int64_t res_F = 0, res_nsig = 0;
     bool res_valid = false;
-    int32_t *d_pid = nullptr, *d_pst = nullptr, *d_pln = nullptr;     // resident partial table
     size_t trk_cap = 0;                    // entries of d_pid / d_pst / d_pln
-    void* d_tws = nullptr;                 // tracker workspace
-    size_t tws_cap = 0;
     int64_t res_P = -1, res_maxend = -1;
-    double* d_w = nullptr;                 // resynthesised waveform
-    size_t w_cap = 0;
-    void* d_sws = nullptr;                 // resynthesis workspace (k_synth.hip)
-    size_t sws_cap = 0;
-    unsigned sws_gen = 0;                  // calls on this workspace since it was allocated
-    void* d_stash = nullptr;               // k_fused_rev: first spectra of its waves, for the waves below them (FusedParams::stash)
-    size_t stash_cap = 0;
-    float* d_x32 = nullptr;                // a device-resident float64 signal narrowed for the fused float32 kernels
-    size_t x32_cap = 0;
-    void* d_desc = nullptr;                // descriptor outputs (f0 / harmonic power)
-    size_t desc_cap = 0;
+    unsigned sws_gen = 0;                  // calls on d_sws since it was allocated
     // optional stage timing (bench): events[4*i..4*i+3] bracket the three stages of chunk i
     bool timing = false;
-    std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
     std::vector<std::pair<int, size_t>> ev_spans;   // (stage, index of the start event; end = next event)
+
+    // ---- what the plan owns (pvx_mem.h).  Members are destroyed last to first: the events, the rocFFT plan, the buffers, and
+    // the streams at the very end.
+    Stream s_host;                         // non-blocking stream of the host entry points
+    Stream s_copy;                         // second stream: DMA of finished waveform slices under the next slice's kernel
+    DevMem d_win;             // window / wfact in the working precision
+    DevMem d_wfbin;           // double [N2]
+    DevMem d_frames;          // [max_rows+1][ldi]
+    DevMem d_spec;            // [max_rows+1][ldo] complex
+    DevMem d_cand_y;          // the split transform's candidate peaks per workspace row (pvx_stft.h): |X|^2 [max_rows+1][cand_cap],
+    DevMem d_cand_bin;        // unsigned short bins, and double [max_rows+1][4] max / min / sum / count
+    DevMem d_cand_stats;
+    DevMem d_rspec;           // rocFFT output when the main spectrum workspace belongs to k_stft
+    DevMem d_twiddle64;       // complex<T>[nfft] W_nfft^j for k_stft (T = the plan's precision)
+    DevMem d_twiddle;         // float2[2048] W_2048^j for the fused kernel
+    DevMem d_specrow;         // 1024 complex float: spectrum of one requested row (fused mode)
+    DevMem d_stash;           // k_fused_rev: first spectra of its waves, for the waves below them (FusedParams::stash)
+    // PVHarmonic: per-frame f0 / previous-row tables and the carried spectrum of the last valid frame
+    DevMem d_hf0;
+    DevMem d_hx;              // pvx_harmonic_analyze: the host signal's device copy (kept: allocating and freeing hundreds of MB
+                              // per call cost more than the analysis)
+    DevMem d_hprev;
+    DevMem d_carry;
+    DevMem d_lastspec;        // k_pv_rev / k_pv_team: double [N2][2] the spectrum of the one row a call asks for (chunk carry, last_spec)
+    DevMem d_pvstage;         // k_pv_rev at nfft 2048: the kept peaks' values between the frames (PvRevParams::stage)
+    DevMem d_wiretmp;         // pvx_analyze_dev_wire on plans whose kernels do not write the wire format themselves: the result block that is then packed
+    // host entry points: plan-owned, grow-only buffers (no hipMalloc / hipFree per call)
+    DevMem d_in[2];           // input chunks (double-buffered: H2D of chunk i+1 under the kernels of chunk i)
+    DevMem d_out[2];          // result blocks of a chunk when the results stream back to the host
+    PinMem h_pin;             // pinned staging of small calls (input, then the result block)
+    PinMem h_ring;            // pinned ring of the threaded staging of large host transfers (kStageThreads x 2 slots)
+    DevMem d_prev;            // double [N2][2] spectrum carried from one input chunk to the next (PV.py:209)
+    DevMem d_res;             // the resident result block
+    DevMem d_pid, d_pst, d_pln;   // resident partial table (int32)
+    DevMem d_tws;             // tracker workspace
+    DevMem d_w;               // resynthesised waveform
+    DevMem d_sws;             // resynthesis workspace (k_synth.hip)
+    DevMem d_x32;             // a device-resident float64 signal narrowed for the fused float32 kernels
+    DevMem d_desc;            // descriptor outputs (f0 / harmonic power)
+    RealFft fft;              // with its work buffer
+    Event ev_done[2];
+    Event ev_ring[16];
+    std::vector<Event> ev_pool;
 };
 static int plan_device(const pvx_plan* p) { return p->device; }
+struct ProgressScope {   // progress_live until the scope ends, however it ends
+    pvx_plan* const p;
+    explicit ProgressScope(pvx_plan* q) : p(q) { p->progress_live = true; }
+    ~ProgressScope() { p->progress_live = false; }
+    ProgressScope(const ProgressScope&) = delete;
+};
 extern "C" int pvx_plan_device(const pvx_plan* plan) { return plan ? plan->device : PVX_ERR_INVALID; }
 extern "C" const char* pvx_plan_last_kernels(const pvx_plan* plan) {
     if (!plan) return "";
@@ -264,59 +260,11 @@ extern "C" const char* pvx_plan_last_kernels(const pvx_plan* plan) {
 
 static size_t real_size(int precision) { return precision == 32 ? 4 : 8; }
 
-static void plan_free(pvx_plan* p) {
-    if (!p) return;
-    for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
-    if (p->info) rocfft_execution_info_destroy(p->info);
-    if (p->fft) rocfft_plan_destroy(p->fft);
-    if (p->d_win) (void)hipFree(p->d_win);
-    if (p->d_wfbin) (void)hipFree(p->d_wfbin);
-    if (p->d_frames) (void)hipFree(p->d_frames);
-    if (p->d_spec) (void)hipFree(p->d_spec);
-    if (p->d_cand_y) (void)hipFree(p->d_cand_y);
-    if (p->d_cand_bin) (void)hipFree(p->d_cand_bin);
-    if (p->d_cand_stats) (void)hipFree(p->d_cand_stats);
-    if (p->d_work) (void)hipFree(p->d_work);
-    if (p->d_rspec) (void)hipFree(p->d_rspec);
-    if (p->d_twiddle64) (void)hipFree(p->d_twiddle64);
-    if (p->d_twiddle) (void)hipFree(p->d_twiddle);
-    if (p->d_specrow) (void)hipFree(p->d_specrow);
-    if (p->d_stash) (void)hipFree(p->d_stash);
-    if (p->d_hf0) (void)hipFree(p->d_hf0);
-    if (p->d_hx) (void)hipFree(p->d_hx);
-    if (p->d_hprev) (void)hipFree(p->d_hprev);
-    if (p->d_carry) (void)hipFree(p->d_carry);
-    if (p->d_lastspec) (void)hipFree(p->d_lastspec);
-    if (p->d_pvstage) (void)hipFree(p->d_pvstage);
-    if (p->d_wiretmp) (void)hipFree(p->d_wiretmp);
-    for (int i = 0; i < 2; i++) {
-        if (p->d_in[i]) (void)hipFree(p->d_in[i]);
-        if (p->d_out[i]) (void)hipFree(p->d_out[i]);
-        if (p->ev_done[i]) (void)hipEventDestroy(p->ev_done[i]);
-    }
-    if (p->h_pin) (void)hipHostFree(p->h_pin);
-    if (p->h_ring) (void)hipHostFree(p->h_ring);
-    for (int i = 0; i < 16; i++) if (p->ev_ring[i]) (void)hipEventDestroy(p->ev_ring[i]);
-    if (p->d_prev) (void)hipFree(p->d_prev);
-    if (p->d_res) (void)hipFree(p->d_res);
-    if (p->d_pid) (void)hipFree(p->d_pid);
-    if (p->d_pst) (void)hipFree(p->d_pst);
-    if (p->d_pln) (void)hipFree(p->d_pln);
-    if (p->d_tws) (void)hipFree(p->d_tws);
-    if (p->d_w) (void)hipFree(p->d_w);
-    if (p->d_sws) (void)hipFree(p->d_sws);
-    if (p->d_x32) (void)hipFree(p->d_x32);
-    if (p->d_desc) (void)hipFree(p->d_desc);
-    if (p->s_host) (void)hipStreamDestroy(p->s_host);
-    if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
-    delete p;
-}
-
 #include "build_sha.inc"
 extern "C" const char* pvx_build_fingerprint(void) { return PVX_BUILD_SHA; }
 
 extern "C" int pvx_plan_destroy(pvx_plan* plan) {
-    plan_free(plan);
+    delete plan;
     return PVX_OK;
 }
 
@@ -377,8 +325,9 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
         return PVX_ERR_INVALID;
     }
     const int64_t rows_hint = max_rows;
-    pvx_plan* p = new pvx_plan();
-    if (hipGetDevice(&p->device) != hipSuccess) { delete p; pvx_set_error("hipGetDevice failed"); return PVX_ERR_HIP; }
+    std::unique_ptr<pvx_plan> owner(new pvx_plan());      // an early return destroys the plan and what it holds so far
+    pvx_plan* p = owner.get();
+    if (hipGetDevice(&p->device) != hipSuccess) { pvx_set_error("hipGetDevice failed"); return PVX_ERR_HIP; }
     p->sr = sr; p->nfft = nfft; p->hop = hop; p->npks = npks; p->pkthresh = pkthresh;
     p->precision = precision;
     p->N2 = nfft / 2;                                   // PV.py:88
@@ -398,7 +347,7 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
     p->wfact = sqrt(wsum2 * nfft) / 2.0;                // PV.py:102
     p->fstep = sr / (double)nfft;                       // PV.py:105
     p->dt = (double)hop / sr;                           // PV.py:108
-    if (!(p->wfact > 0)) { pvx_set_error("window has no energy"); plan_free(p); return PVX_ERR_INVALID; }
+    if (!(p->wfact > 0)) { pvx_set_error("window has no energy"); return PVX_ERR_INVALID; }
 
     const size_t rs = real_size(precision);
     // Launch size: the frame + spectrum workspace of one launch (~96 MiB by default) stays inside
@@ -431,21 +380,21 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
             const double dthetabin = pi2 * fbin * p->dt;                // PV.py:116
             wf[k] = nearbyint(dthetabin / pi2) * pi2;                   // PV.py:118 (np.round: half to even)
         }
-        if (hipMalloc(&p->d_wfbin, sizeof(double) * wf.size()) != hipSuccess) { pvx_set_error("hipMalloc(wfbin) failed"); plan_free(p); return PVX_ERR_ALLOC; }
-        if (hipMemcpy(p->d_wfbin, wf.data(), sizeof(double) * wf.size(), hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(wfbin) failed"); plan_free(p); return PVX_ERR_HIP; }
+        if (p->d_wfbin.alloc(sizeof(double) * wf.size()) != PVX_OK) { pvx_set_error("hipMalloc(wfbin) failed"); return PVX_ERR_ALLOC; }
+        if (hipMemcpy(p->d_wfbin.get(), wf.data(), sizeof(double) * wf.size(), hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(wfbin) failed"); return PVX_ERR_HIP; }
         // window with 1/wfact folded in (fft(x*win)/wfact, PV.py:156-157)
-        if (hipMalloc(&p->d_win, rs * nfft) != hipSuccess) { pvx_set_error("hipMalloc(win) failed"); plan_free(p); return PVX_ERR_ALLOC; }
+        if (p->d_win.alloc(rs * nfft) != PVX_OK) { pvx_set_error("hipMalloc(win) failed"); return PVX_ERR_ALLOC; }
         hipError_t e;
         if (precision == 32) {
             std::vector<float> w(nfft);
             for (int i = 0; i < nfft; i++) w[i] = (float)(p->win[i] / p->wfact);
-            e = hipMemcpy(p->d_win, w.data(), rs * nfft, hipMemcpyHostToDevice);
+            e = hipMemcpy(p->d_win.get(), w.data(), rs * nfft, hipMemcpyHostToDevice);
         } else {
             std::vector<double> w(nfft);
             for (int i = 0; i < nfft; i++) w[i] = p->win[i] / p->wfact;
-            e = hipMemcpy(p->d_win, w.data(), rs * nfft, hipMemcpyHostToDevice);
+            e = hipMemcpy(p->d_win.get(), w.data(), rs * nfft, hipMemcpyHostToDevice);
         }
-        if (e != hipSuccess) { pvx_set_error("hipMemcpy(win) failed"); plan_free(p); return PVX_ERR_HIP; }
+        if (e != hipSuccess) { pvx_set_error("hipMemcpy(win) failed"); return PVX_ERR_HIP; }
     }
 
     // float64 fused STFT kernel (k_stft.hip): its own twiddle table; the spectrum workspace is the only intermediate
@@ -466,8 +415,8 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
         for (int j = 0; j < nfft; j++) { tw[2 * j] = cos(2.0 * pi * j / (double)nfft); tw[2 * j + 1] = -sin(2.0 * pi * j / (double)nfft); }
         std::vector<float> twf(tw.begin(), tw.end());
         const void* src = precision == 64 ? (const void*)tw.data() : (const void*)twf.data();
-        if (hipMalloc(&p->d_twiddle64, tw.size() * rs) != hipSuccess) { pvx_set_error("hipMalloc(stft twiddle) failed"); plan_free(p); return PVX_ERR_ALLOC; }
-        if (hipMemcpy(p->d_twiddle64, src, tw.size() * rs, hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(stft twiddle) failed"); plan_free(p); return PVX_ERR_HIP; }
+        if (p->d_twiddle64.alloc(tw.size() * rs) != PVX_OK) { pvx_set_error("hipMalloc(stft twiddle) failed"); return PVX_ERR_ALLOC; }
+        if (hipMemcpy(p->d_twiddle64.get(), src, tw.size() * rs, hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(stft twiddle) failed"); return PVX_ERR_HIP; }
         // nfft 512 .. 2048: the peaks found in the transform's launch; at float64 with npks <= 64 the spectrum rows kept on chip
         p->general = Route::stft_peaks;
         if (pvx_stft_pv_supported(nfft, precision, npks) && !getenv("PVX_NO_STFT_PV"))
@@ -493,8 +442,8 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
         const double pi = 3.141592653589793238462643383279502884;
         for (int j = 0; j < nfft; j++) { tw[2 * j] = (float)cos(2.0 * pi * j / (double)nfft); tw[2 * j + 1] = (float)(-sin(2.0 * pi * j / (double)nfft)); }
         if (ntt) pvx_fused_team_table(nfft, tw.data(), tw.data() + 2 * (size_t)nfft);
-        if (hipMalloc(&p->d_twiddle, tw.size() * 4) != hipSuccess || hipMalloc((void**)&p->d_specrow, (size_t)nfft * 4) != hipSuccess) { pvx_set_error("hipMalloc(fused tables) failed"); plan_free(p); return PVX_ERR_ALLOC; }
-        if (hipMemcpy(p->d_twiddle, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(twiddle) failed"); plan_free(p); return PVX_ERR_HIP; }
+        if (p->d_twiddle.alloc(tw.size() * 4) != PVX_OK || p->d_specrow.alloc((size_t)nfft * 4) != PVX_OK) { pvx_set_error("hipMalloc(fused tables) failed"); return PVX_ERR_ALLOC; }
+        if (hipMemcpy(p->d_twiddle.get(), tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { pvx_set_error("hipMemcpy(twiddle) failed"); return PVX_ERR_HIP; }
         // default: one wave per frame where it exists (nfft <= 2048: independent waves walking their rows downwards
         // over one buffer each, k_fused_rev.hip, while npks leaves them enough LDS), several waves per frame above
         // (nfft 4096 / 8192: teams of such waves, k_fused_team.hip, while npks <= 128; the general path beyond -- and wherever
@@ -506,7 +455,7 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
         }
         if (const char* e = getenv("PVX_FUSED_BLOCKS")) { const long long v = atoll(e); if (v > 0) p->fused_blocks = v; }
     }
-    *out = p;
+    *out = owner.release();
     return PVX_OK;
 }
 
@@ -514,7 +463,7 @@ extern "C" int pvx_plan_create(pvx_plan** out, double sr, int nfft, int hop, int
 static int ensure_spec_ws(pvx_plan* p) {
     if (p->d_spec) return PVX_OK;
     const size_t sbytes = (size_t)(p->max_rows + 1) * p->ldo * 2 * real_size(p->precision);
-    if (hipMalloc(&p->d_spec, sbytes) != hipSuccess) { pvx_set_error("hipMalloc of %.1f MiB spectrum workspace failed", sbytes / 1048576.0); p->d_spec = nullptr; return PVX_ERR_ALLOC; }
+    if (p->d_spec.alloc(sbytes) != PVX_OK) { pvx_set_error("hipMalloc of %.1f MiB spectrum workspace failed", sbytes / 1048576.0); return PVX_ERR_ALLOC; }
     p->ws_bytes += (int64_t)sbytes;
     return PVX_OK;
 }
@@ -549,13 +498,10 @@ static int ensure_cand_ws(pvx_plan* p) {
     if (p->d_cand_bin) return PVX_OK;
     const int cap = p->N2 / 2 + 8;
     const size_t rows = (size_t)p->max_rows + 1, rs = real_size(p->precision);
-    if (hipMalloc(&p->d_cand_y, rows * cap * rs) != hipSuccess || hipMalloc((void**)&p->d_cand_bin, rows * cap * 2) != hipSuccess ||
-        hipMalloc((void**)&p->d_cand_stats, rows * 4 * sizeof(double)) != hipSuccess) {
+    if (p->d_cand_y.alloc(rows * cap * rs) != PVX_OK || p->d_cand_bin.alloc(rows * cap * 2) != PVX_OK ||
+        p->d_cand_stats.alloc(rows * 4 * sizeof(double)) != PVX_OK) {
+        p->d_cand_y.reset(); p->d_cand_bin.reset(); p->d_cand_stats.reset();
         pvx_set_error("hipMalloc of the candidate workspace failed");
-        if (p->d_cand_y) (void)hipFree(p->d_cand_y);
-        if (p->d_cand_bin) (void)hipFree(p->d_cand_bin);
-        if (p->d_cand_stats) (void)hipFree(p->d_cand_stats);
-        p->d_cand_y = nullptr; p->d_cand_bin = nullptr; p->d_cand_stats = nullptr;
         return PVX_ERR_ALLOC;
     }
     p->cand_cap = cap;
@@ -566,13 +512,11 @@ static int ensure_cand_ws(pvx_plan* p) {
 // frames + spectrum workspace and the rocFFT plan (fft mode 0, calc_fft_frame): created on first use.
 // With k_stft in charge of the analysis the rocFFT side only serves pvx_stft_frames: two rows, its own output.
 static void release_rocfft(pvx_plan* p) {
-    if (p->info) { rocfft_execution_info_destroy(p->info); p->info = nullptr; }
-    if (p->fft) { rocfft_plan_destroy(p->fft); p->fft = nullptr; }
-    if (p->d_frames) { (void)hipFree(p->d_frames); p->d_frames = nullptr; }
-    if (p->d_rspec) { (void)hipFree(p->d_rspec); p->d_rspec = nullptr; }
-    if (p->d_work) { (void)hipFree(p->d_work); p->d_work = nullptr; }
-    if (!p->rocfft_small && !has_stft(p) && p->d_spec) { (void)hipFree(p->d_spec); p->d_spec = nullptr; }
-    p->rocfft_ready = false; p->rocfft_small = false; p->work_bytes = 0;
+    p->fft.reset();
+    p->d_frames.reset();
+    p->d_rspec.reset();
+    if (!p->rocfft_small && !has_stft(p)) p->d_spec.reset();
+    p->rocfft_ready = false; p->rocfft_small = false;
 }
 
 // full = the analysis itself goes through rocFFT (fft mode 0 without k_stft, PVHarmonic at float32): workspace of
@@ -587,39 +531,27 @@ static int ensure_rocfft(pvx_plan* p, bool full) {
     const int64_t ws_rows = max_rows + 1;
     p->rocfft_rows = max_rows;
     const size_t fbytes = (size_t)ws_rows * p->ldi * rs, sbytes = (size_t)ws_rows * p->ldo * 2 * rs;
-    void** specp = small ? &p->d_rspec : &p->d_spec;
+    DevMem& spec = small ? p->d_rspec : p->d_spec;
     p->rocfft_small = small;
-    if (hipMalloc(&p->d_frames, fbytes) != hipSuccess || hipMalloc(specp, sbytes) != hipSuccess) {
+    if (p->d_frames.alloc(fbytes) != PVX_OK || spec.alloc(sbytes) != PVX_OK) {
         pvx_set_error("hipMalloc of %.1f MiB analysis workspace failed", (fbytes + sbytes) / 1048576.0);
-        if (p->d_frames) { (void)hipFree(p->d_frames); p->d_frames = nullptr; }
-        if (*specp) { (void)hipFree(*specp); *specp = nullptr; }
+        p->d_frames.reset();
         return PVX_ERR_ALLOC;
     }
     // rocFFT: batched 1-D real -> hermitian, one transform per workspace row (PV.py:157)
-    rocfft_plan_description desc = nullptr;
-    rocfft_status st = rocfft_plan_description_create(&desc);
-    if (st == rocfft_status_success) {
-        size_t istride = 1, ostride = 1;
-        st = rocfft_plan_description_set_data_layout(desc, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved,
-                                                     nullptr, nullptr, 1, &istride, (size_t)p->ldi, 1, &ostride, (size_t)p->ldo);
+    rocfft_status st;
+    switch (p->fft.create((size_t)nfft, (size_t)ws_rows, precision == 32 ? rocfft_precision_single : rocfft_precision_double,
+                          rocfft_placement_notinplace, (size_t)p->ldi, (size_t)p->ldo, &st)) {
+        case RealFft::done: break;
+        case RealFft::info: pvx_set_error("rocfft work buffer query failed: %d", (int)st); return PVX_ERR_HIP;
+        default: pvx_set_error("rocfft_plan_create(nfft=%d, batch=%lld) failed: %d", nfft, (long long)ws_rows, (int)st); return PVX_ERR_HIP;
     }
-    if (st == rocfft_status_success) {
-        size_t len = (size_t)nfft;
-        st = rocfft_plan_create(&p->fft, rocfft_placement_notinplace, rocfft_transform_type_real_forward,
-                                precision == 32 ? rocfft_precision_single : rocfft_precision_double, 1, &len,
-                                (size_t)ws_rows, desc);
-    }
-    if (desc) rocfft_plan_description_destroy(desc);
-    if (st != rocfft_status_success) { pvx_set_error("rocfft_plan_create(nfft=%d, batch=%lld) failed: %d", nfft, (long long)ws_rows, (int)st); return PVX_ERR_HIP; }
-    st = rocfft_plan_get_work_buffer_size(p->fft, &p->work_bytes);
-    if (st == rocfft_status_success) st = rocfft_execution_info_create(&p->info);
-    if (st != rocfft_status_success) { pvx_set_error("rocfft work buffer query failed: %d", (int)st); return PVX_ERR_HIP; }
-    if (p->work_bytes) {
-        if (hipMalloc(&p->d_work, p->work_bytes) != hipSuccess) { pvx_set_error("hipMalloc(rocfft work, %zu) failed", p->work_bytes); return PVX_ERR_ALLOC; }
-        st = rocfft_execution_info_set_work_buffer(p->info, p->d_work, p->work_bytes);
+    if (const size_t wb = p->fft.work_bytes()) {
+        if (p->fft.work.alloc(wb) != PVX_OK) { pvx_set_error("hipMalloc(rocfft work, %zu) failed", wb); return PVX_ERR_ALLOC; }
+        st = p->fft.set_work(p->fft.work.get(), wb);
         if (st != rocfft_status_success) { pvx_set_error("rocfft set_work_buffer failed: %d", (int)st); return PVX_ERR_HIP; }
     }
-    p->ws_bytes += (int64_t)(fbytes + sbytes + p->work_bytes);
+    p->ws_bytes += (int64_t)(fbytes + sbytes + p->fft.work_bytes());
     p->rocfft_ready = true;
     return PVX_OK;
 }
@@ -656,9 +588,9 @@ extern "C" int pvx_plan_set_timing(pvx_plan* plan, int enable) {
 static int plan_event(pvx_plan* p, hipStream_t s, int stage) {
     if (!p->timing) return PVX_OK;
     if (p->ev_used == p->ev_pool.size()) {
-        hipEvent_t e;
-        PVX_HIP_CHECK(hipEventCreate(&e));
-        p->ev_pool.push_back(e);
+        Event e;
+        PVX_HIP_CHECK(e.ensure(hipEventDefault));
+        p->ev_pool.push_back(std::move(e));
     }
     if (stage >= 0) p->ev_spans.push_back(std::make_pair(stage, p->ev_used));
     PVX_HIP_CHECK(hipEventRecord(p->ev_pool[p->ev_used++], s));
@@ -689,25 +621,22 @@ struct SpecRequest { int64_t row = -1; float* host = nullptr; };
 // where `route` left the spectrum row its call asked for (the call's last row `row`): [N2] complex, float32 or float64
 struct SpecRow { const void* d; bool f32; };
 static SpecRow spec_row_at(const pvx_plan* p, Route route, int64_t row) {
-    if (is_fused(route)) return {p->d_specrow, true};
-    if (route == Route::pv_rev || route == Route::pv_team) return {p->d_lastspec, false};
+    if (is_fused(route)) return {p->d_specrow.as<float>(), true};
+    if (route == Route::pv_rev || route == Route::pv_team) return {p->d_lastspec.as<double>(), false};
     const int64_t wsrow = row % p->max_rows + 1;             // in the last chunk's workspace
-    return {(const char*)p->d_spec + (size_t)wsrow * p->ldo * 2 * real_size(p->precision), p->precision == 32};
+    return {p->d_spec.as<const char>() + (size_t)wsrow * p->ldo * 2 * real_size(p->precision), p->precision == 32};
 }
 
 // window + FFT of a chunk's workspace rows into d_spec: k_stft, or k_frames + rocFFT (stage events 0 and 1)
 static int launch_transform(pvx_plan* p, const FrameParams& fp, int x_dtype, hipStream_t s) {
     int rc;
     if ((rc = plan_event(p, s, 0)) != PVX_OK) return rc;
-    if (has_stft(p)) return pvx_launch_stft(fp, p->d_spec, p->ldo, p->d_twiddle64, x_dtype, p->precision, s);
+    if (has_stft(p)) return pvx_launch_stft(fp, p->d_spec.get(), p->ldo, p->d_twiddle64.get(), x_dtype, p->precision, s);
     if ((rc = pvx_launch_frames(fp, x_dtype, p->precision, s)) != PVX_OK || (rc = plan_event(p, s, 1)) != PVX_OK) return rc;
-    void* in[1] = {p->d_frames}, *out[1] = {p->d_spec};
-    PVX_FFT_CHECK(rocfft_execution_info_set_stream(p->info, s));
-    PVX_FFT_CHECK(rocfft_execute(p->fft, in, out, p->info));
+    PVX_FFT_CHECK(p->fft.execute(p->d_frames.get(), p->d_spec.get(), s));
     return PVX_OK;
 }
 
-template <typename T> static int grow_dev(T** p, size_t* cap, size_t need);
 // The analysis of a call by `route` (route_for), which the plan records.  wire_out: d_f / d_mag / d_ph / d_binno / d_totalmag
 // are the sections of a wire block (pvx_analyze_dev_wire): only k_fused_rev writes it itself.
 static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, int64_t nsamp, int64_t nsig, int64_t sig_stride,
@@ -725,18 +654,18 @@ static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, 
             // is (float) x[n] -- done here in one pass, so that they exist for float32 and int16 samples only (a float64
             // sample pair per lane and row cost them registers they do not have)
             const size_t nel = (size_t)((nsig - 1) * sig_stride + nsamp);
-            if ((rc = grow_dev(&p->d_x32, &p->x32_cap, nel * 4)) != PVX_OK) return rc;
-            if ((rc = pvx_launch_narrow((const double*)d_x, p->d_x32, (int64_t)nel, s)) != PVX_OK) return rc;
-            d_x = p->d_x32; x_dtype = PVX_F32;
+            if ((rc = p->d_x32.grow(nel * 4, Sizing::headroom)) != PVX_OK) return rc;
+            if ((rc = pvx_launch_narrow((const double*)d_x, p->d_x32.as<float>(), (int64_t)nel, s)) != PVX_OK) return rc;
+            d_x = p->d_x32.as<float>(); x_dtype = PVX_F32;
         }
         FusedParams fp;
         fp.x = d_x; fp.sig_stride = sig_stride; fp.F = F; fp.total_rows = total_rows;
         fp.hop = p->hop; fp.K = p->npks; fp.rad = 5;                                     // PV.py:177
         fp.thr = p->pkthresh; fp.sr = p->sr; fp.fstep = p->fstep; fp.dt = p->dt;
-        fp.wfbin = p->d_wfbin; fp.prev0 = d_prev0;
+        fp.wfbin = p->d_wfbin.as<double>(); fp.prev0 = d_prev0;
         fp.f = d_f; fp.mag = d_mag; fp.ph = d_ph; fp.realph = d_realph; fp.binno = d_binno;
-        fp.t = d_t; fp.totalmag = d_totalmag; fp.win = p->d_win; fp.twiddle = p->d_twiddle;
-        fp.spec_out = spec.row >= 0 ? (spec.host ? spec.host : p->d_specrow) : nullptr; fp.spec_row = spec.row;
+        fp.t = d_t; fp.totalmag = d_totalmag; fp.win = p->d_win.get(); fp.twiddle = p->d_twiddle.get();
+        fp.spec_out = spec.row >= 0 ? (spec.host ? spec.host : p->d_specrow.as<float>()) : nullptr; fp.spec_row = spec.row;
         fp.blocks_override = p->fused_blocks;
         fp.stash = nullptr; fp.stash_bytes = 0;
         fp.wire = wire_out ? p->wire_fmt : 0;
@@ -746,10 +675,9 @@ static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, 
                 FusedParams q = fp;
                 q.total_rows = (int64_t)1 << 30;
                 const size_t need = pvx_fused_rev_stash_bytes(q, p->nfft);
-                if (need > 0 && hipMalloc(&p->d_stash, need) == hipSuccess) p->stash_cap = need;
-                else { p->d_stash = nullptr; p->stash_cap = 0; (void)hipGetLastError(); }     // (without it the waves compute that row themselves)
+                if (need > 0 && p->d_stash.alloc(need) != PVX_OK) (void)hipGetLastError();   // not an error: without it the waves compute that row themselves
             }
-            fp.stash = p->d_stash; fp.stash_bytes = p->stash_cap;
+            fp.stash = p->d_stash.get(); fp.stash_bytes = p->d_stash.cap();
         }
         if ((rc = plan_event(p, s, 3)) != PVX_OK) return rc;
         switch (route) {
@@ -769,13 +697,13 @@ static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, 
         rp.x = d_x; rp.sig_stride = sig_stride; rp.F = F; rp.total_rows = total_rows;
         rp.hop = p->hop; rp.K = p->npks; rp.rad = 5;                                     // PV.py:177
         rp.thr = p->pkthresh; rp.sr = p->sr; rp.fstep = p->fstep; rp.dt = p->dt;
-        rp.wfbin = p->d_wfbin; rp.prev0 = d_prev0;
+        rp.wfbin = p->d_wfbin.as<double>(); rp.prev0 = d_prev0;
         rp.f = d_f; rp.mag = d_mag; rp.ph = d_ph; rp.realph = d_realph; rp.binno = d_binno;
-        rp.t = d_t; rp.totalmag = d_totalmag; rp.win = p->d_win; rp.twiddle = p->d_twiddle64;
+        rp.t = d_t; rp.totalmag = d_totalmag; rp.win = p->d_win.get(); rp.twiddle = p->d_twiddle64.get();
         rp.spec_out = nullptr; rp.spec_row = spec.row;
         if (spec.row >= 0) {
-            if (!p->d_lastspec) PVX_HIP_CHECK(hipMalloc((void**)&p->d_lastspec, sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1)));
-            rp.spec_out = p->d_lastspec;
+            if (!p->d_lastspec && (rc = p->d_lastspec.alloc(sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1))) != PVX_OK) return rc;
+            rp.spec_out = p->d_lastspec.as<double>();
         }
         rp.blocks_override = 0;
         if (const char* e = getenv("PVX_PV_REV_BLOCKS")) { const long long v = atoll(e); if (v >= 1) rp.blocks_override = v; }   // tests: other grids
@@ -783,8 +711,8 @@ static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, 
         rp.stage = nullptr; rp.stage_bytes = 0;
         const size_t need = team ? pvx_pv_team_stage_bytes(p->nfft) : pvx_pv_rev_stage_bytes(p->nfft);
         if (need > 0) {
-            if ((rc = grow_dev(&p->d_pvstage, &p->pvstage_cap, need)) != PVX_OK) return rc;
-            rp.stage = p->d_pvstage; rp.stage_bytes = p->pvstage_cap;
+            if ((rc = p->d_pvstage.grow(need, Sizing::headroom)) != PVX_OK) return rc;
+            rp.stage = p->d_pvstage.get(); rp.stage_bytes = p->d_pvstage.cap();
         }
         // one launch -- unless the caller set PVX_MAX_ROWS: then pieces of that many rows, each reported (tests, progress displays)
         const int64_t piece = p->rows_from_env ? p->max_rows : total_rows;
@@ -806,23 +734,23 @@ static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, 
         FrameParams fp;
         fp.x = d_x; fp.nsamp = nsamp; fp.sig_stride = sig_stride; fp.F = F; fp.R0 = R0;
         fp.ws_rows = nrows + 1; fp.total_rows = total_rows; fp.nfft = p->nfft; fp.hop = p->hop;
-        fp.win = p->d_win; fp.frames = p->d_frames; fp.ldi = p->ldi; fp.win_symmetric = p->win_symmetric ? 1 : 0;
+        fp.win = p->d_win.get(); fp.frames = p->d_frames.get(); fp.ldi = p->ldi; fp.win_symmetric = p->win_symmetric ? 1 : 0;
         PeaksParams pp;
-        pp.spec = p->d_spec; pp.ldo = p->ldo; pp.F = F; pp.R0 = R0; pp.nrows = nrows;
+        pp.spec = p->d_spec.get(); pp.ldo = p->ldo; pp.F = F; pp.R0 = R0; pp.nrows = nrows;
         pp.nfft = p->nfft; pp.hop = p->hop; pp.N2 = p->N2; pp.K = p->npks; pp.rad = 5;   // PV.py:177
         pp.thr = p->pkthresh; pp.sr = p->sr; pp.fstep = p->fstep; pp.dt = p->dt;
-        pp.wfbin = p->d_wfbin; pp.prev0 = d_prev0;
+        pp.wfbin = p->d_wfbin.as<double>(); pp.prev0 = d_prev0;
         pp.f = d_f; pp.mag = d_mag; pp.ph = d_ph; pp.realph = d_realph; pp.binno = d_binno;
         pp.t = d_t; pp.totalmag = d_totalmag; pp.frames_per_wave = p->frames_per_wave;
         if (cand) {
-            fp.cand_y = p->d_cand_y; fp.cand_bin = p->d_cand_bin; fp.cand_stats = p->d_cand_stats; fp.cand_cap = p->cand_cap; fp.cand_thr = p->pkthresh;
-            pp.cand_y = p->d_cand_y; pp.cand_bin = p->d_cand_bin; pp.cand_stats = p->d_cand_stats; pp.cand_cap = p->cand_cap;
+            fp.cand_y = p->d_cand_y.get(); fp.cand_bin = p->d_cand_bin.as<unsigned short>(); fp.cand_stats = p->d_cand_stats.as<double>(); fp.cand_cap = p->cand_cap; fp.cand_thr = p->pkthresh;
+            pp.cand_y = p->d_cand_y.get(); pp.cand_bin = p->d_cand_bin.as<unsigned short>(); pp.cand_stats = p->d_cand_stats.as<double>(); pp.cand_cap = p->cand_cap;
         }
         if (route == Route::stft_pv) {
             // window + FFT + untangle + peaks of every row in one kernel (k_stft_pv.hip); the spectrum rows still land in
             // the workspace
             if ((rc = plan_event(p, s, 3)) != PVX_OK) return rc;
-            if ((rc = pvx_launch_stft_pv(fp, pp, p->d_spec, p->ldo, p->d_twiddle64, x_dtype, p->precision, s)) != PVX_OK) return rc;
+            if ((rc = pvx_launch_stft_pv(fp, pp, p->d_spec.get(), p->ldo, p->d_twiddle64.get(), x_dtype, p->precision, s)) != PVX_OK) return rc;
         } else {
             if ((rc = launch_transform(p, fp, x_dtype, s)) != PVX_OK) return rc;
             if ((rc = plan_event(p, s, 2)) != PVX_OK) return rc;
@@ -863,41 +791,9 @@ extern "C" int64_t pvx_analyze_dev(pvx_plan* p, const void* d_x, int x_dtype, in
 
 static size_t dtype_size(int x_dtype) { return x_dtype == PVX_F32 ? 4 : (x_dtype == PVX_F64 ? 8 : 2); }
 
-namespace {
-struct DevBuf {   // RAII for the host-buffer wrappers
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { pvx_set_error("hipMalloc(%zu) failed", bytes); p = nullptr; return PVX_ERR_ALLOC; }
-        return PVX_OK;
-    }
-};
-}  // namespace
-
-// grow-only device / pinned buffers owned by the plan
-template <typename T> static int grow_dev(T** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return PVX_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = need + need / 4 + 256;
-    if (hipMalloc((void**)p, want) != hipSuccess) {
-        if (hipMalloc((void**)p, need ? need : 1) != hipSuccess) { pvx_set_error("hipMalloc(%zu) failed", need); *p = nullptr; return PVX_ERR_ALLOC; }
-        *cap = need;
-        return PVX_OK;
-    }
-    *cap = want;
-    return PVX_OK;
-}
-static int grow_pin(pvx_plan* p, size_t need) {
-    if (need <= p->pin_cap && p->h_pin) return PVX_OK;
-    if (p->h_pin) { (void)hipHostFree(p->h_pin); p->h_pin = nullptr; p->pin_cap = 0; }
-    if (hipHostMalloc(&p->h_pin, need, hipHostMallocDefault) != hipSuccess) { pvx_set_error("hipHostMalloc(%zu) failed", need); return PVX_ERR_ALLOC; }
-    p->pin_cap = need;
-    return PVX_OK;
-}
 static int host_stream(pvx_plan* p) {
-    if (!p->s_host) PVX_HIP_CHECK(hipStreamCreateWithFlags(&p->s_host, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++)
-        if (!p->ev_done[i]) PVX_HIP_CHECK(hipEventCreateWithFlags(&p->ev_done[i], hipEventDisableTiming));
+    PVX_HIP_CHECK(p->s_host.ensure(hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) PVX_HIP_CHECK(p->ev_done[i].ensure(hipEventDisableTiming));
     return PVX_OK;
 }
 
@@ -912,24 +808,22 @@ static const int kStageThreads = [] { const char* e = getenv("PVX_STAGE_THREADS"
 static const size_t kStagePiece = [] { const char* e = getenv("PVX_STAGE_PIECE_MB"); const int v = e ? atoi(e) : 0; return (size_t)((v >= 1 && v <= 16) ? v : 4) << 20; }();
 static const size_t kStageMin = (size_t)16 << 20;           // below this a plain copy is as good
 
-struct StageRing { void** h_ring; hipEvent_t* ev_ring; };     // a plan's ring, or the process-wide one of the plan-less entry points
+struct StageRing { PinMem& h_ring; Event* ev_ring; };         // a plan's ring, or the process-wide one of the plan-less entry points
 static int stage_ring(StageRing r) {
-    if (!*r.h_ring && hipHostMalloc(r.h_ring, kStagePiece * 2 * kStageThreads, hipHostMallocDefault) != hipSuccess) {
-        *r.h_ring = nullptr; pvx_set_error("hipHostMalloc(staging ring) failed"); return PVX_ERR_ALLOC;
-    }
-    for (int i = 0; i < 16; i++)
-        if (!r.ev_ring[i]) PVX_HIP_CHECK(hipEventCreateWithFlags(&r.ev_ring[i], hipEventDisableTiming));
+    if (!r.h_ring && r.h_ring.alloc(kStagePiece * 2 * kStageThreads) != PVX_OK) { pvx_set_error("hipHostMalloc(staging ring) failed"); return PVX_ERR_ALLOC; }
+    for (int i = 0; i < 16; i++) PVX_HIP_CHECK(r.ev_ring[i].ensure(hipEventDisableTiming));
     return PVX_OK;
 }
-static int stage_ring(pvx_plan* p) { return stage_ring(StageRing{&p->h_ring, p->ev_ring}); }
+static int stage_ring(pvx_plan* p) { return stage_ring(StageRing{p->h_ring, p->ev_ring}); }
 
 // narrow: `host` holds float64 samples and the device gets them as float32 (`bytes` counts the float32 bytes): every
 // precision-32 kernel's first step is (float) x[n], so the staging threads do it while they copy -- the same rounding, half
 // the bytes over the link.
-static int staged_copy(StageRing p_, void* dev, void* host, size_t bytes, bool to_device, hipStream_t s, bool narrow = false) {
-    int rc = stage_ring(p_);
+static int staged_copy(StageRing ring, void* dev, void* host, size_t bytes, bool to_device, hipStream_t s, bool narrow = false) {
+    int rc = stage_ring(ring);
     if (rc != PVX_OK) return rc;
-    struct { void* h_ring; hipEvent_t* ev_ring; } pp = {*p_.h_ring, p_.ev_ring}, *p = &pp;
+    char* const h_ring = ring.h_ring.as<char>();
+    Event* const ev_ring = ring.ev_ring;
     int devid = 0;
     (void)hipGetDevice(&devid);
     const size_t npieces = (bytes + kStagePiece - 1) / kStagePiece;
@@ -939,28 +833,28 @@ static int staged_copy(StageRing p_, void* dev, void* host, size_t bytes, bool t
         size_t k = 0;
         for (size_t i = (size_t)t; i < npieces; i += nthreads, k++) {
             const int slot = 2 * t + (int)(k & 1);
-            char* pin = (char*)p->h_ring + (size_t)slot * kStagePiece;
+            char* pin = h_ring + (size_t)slot * kStagePiece;
             const size_t o = i * kStagePiece, c = bytes - o < kStagePiece ? bytes - o : kStagePiece;
             if (to_device) {
                 // the slot's previous DMA has read it -- of this call or of an earlier one on the same ring (nothing orders
                 // the host against those but this event; on an event never recorded the wait returns at once)
-                if (hipEventSynchronize(p->ev_ring[slot]) != hipSuccess) { err[t] = 1; return; }
+                if (hipEventSynchronize(ev_ring[slot]) != hipSuccess) { err[t] = 1; return; }
                 if (narrow) narrow_f64_f32((const double*)host + o / 4, (float*)pin, c / 4);
                 else memcpy(pin, (const char*)host + o, c);
-                if (hipMemcpyAsync((char*)dev + o, pin, c, hipMemcpyHostToDevice, s) != hipSuccess || hipEventRecord(p->ev_ring[slot], s) != hipSuccess) { err[t] = 1; return; }
+                if (hipMemcpyAsync((char*)dev + o, pin, c, hipMemcpyHostToDevice, s) != hipSuccess || hipEventRecord(ev_ring[slot], s) != hipSuccess) { err[t] = 1; return; }
             } else {
                 // two DMAs of this thread in flight: piece k+1 lands while piece k is copied out
                 if (k == 0) {
-                    if (hipMemcpyAsync(pin, (const char*)dev + o, c, hipMemcpyDeviceToHost, s) != hipSuccess || hipEventRecord(p->ev_ring[slot], s) != hipSuccess) { err[t] = 1; return; }
+                    if (hipMemcpyAsync(pin, (const char*)dev + o, c, hipMemcpyDeviceToHost, s) != hipSuccess || hipEventRecord(ev_ring[slot], s) != hipSuccess) { err[t] = 1; return; }
                 }
                 const size_t in = i + nthreads;
                 if (in < npieces) {
                     const int ns = 2 * t + (int)((k + 1) & 1);
                     const size_t no = in * kStagePiece, nc = bytes - no < kStagePiece ? bytes - no : kStagePiece;
-                    if (hipMemcpyAsync((char*)p->h_ring + (size_t)ns * kStagePiece, (const char*)dev + no, nc, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                        hipEventRecord(p->ev_ring[ns], s) != hipSuccess) { err[t] = 1; return; }
+                    if (hipMemcpyAsync(h_ring + (size_t)ns * kStagePiece, (const char*)dev + no, nc, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipEventRecord(ev_ring[ns], s) != hipSuccess) { err[t] = 1; return; }
                 }
-                if (hipEventSynchronize(p->ev_ring[slot]) != hipSuccess) { err[t] = 1; return; }
+                if (hipEventSynchronize(ev_ring[slot]) != hipSuccess) { err[t] = 1; return; }
                 memcpy((char*)host + o, pin, c);
             }
         }
@@ -985,7 +879,7 @@ static int staged_copy(StageRing p_, void* dev, void* host, size_t bytes, bool t
 }
 
 static int staged_copy(pvx_plan* p, void* dev, void* host, size_t bytes, bool to_device, hipStream_t s, bool narrow = false) {
-    return staged_copy(StageRing{&p->h_ring, p->ev_ring}, dev, host, bytes, to_device, s, narrow);
+    return staged_copy(StageRing{p->h_ring, p->ev_ring}, dev, host, bytes, to_device, s, narrow);
 }
 // Transfers between the CALLER's arrays and device memory.  A hipMemcpy of a pageable array of 1 MB or more makes the
 // runtime register (pin in place) that memory; when the caller frees the array -- result arrays: every call -- the next
@@ -994,8 +888,8 @@ static int staged_copy(pvx_plan* p, void* dev, void* host, size_t bytes, bool to
 // pageable ones through the threaded ring, the ones in between bounce through the process-wide ring's memory.
 static const size_t kDirectMax = (size_t)512 << 10;
 static const int kMaxDevices = 16;
-struct DevRing { void* ring = nullptr; hipEvent_t ev[16] = {}; std::mutex mu; };   // one per device: its events belong to that device
-static DevRing g_rings[kMaxDevices];
+struct DevRing { PinMem ring; Event ev[16]; std::mutex mu; };   // one per device: its events belong to that device
+static DevRing* const g_rings = new DevRing[kMaxDevices];        // (for the process: never deleted, pvx_mem.h)
 static bool host_is_pinned(const void* host) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, host) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -1012,8 +906,7 @@ static int user_copy(void* dev, void* host, size_t bytes, bool to_device) {
     (void)hipGetDevice(&devid);
     DevRing& dr = g_rings[devid >= 0 && devid < kMaxDevices ? devid : 0];
     std::lock_guard<std::mutex> lk(dr.mu);
-    void*& g_ring = dr.ring;
-    const StageRing ring{&dr.ring, dr.ev};
+    const StageRing ring{dr.ring, dr.ev};
     if (bytes >= kStageMin && getenv("PVX_NO_STAGE_THREADS") == nullptr) {
         const int rc = staged_copy(ring, dev, host, bytes, to_device, nullptr);
         if (rc != PVX_OK) return rc;
@@ -1023,6 +916,7 @@ static int user_copy(void* dev, void* host, size_t bytes, bool to_device) {
     int rc = stage_ring(ring);
     if (rc != PVX_OK) return rc;
     const size_t cap = kStagePiece * 2 * kStageThreads;
+    void* const g_ring = dr.ring.get();
     for (size_t o = 0; o < bytes; o += cap) {
         const size_t c = bytes - o < cap ? bytes - o : cap;
         if (to_device) {
@@ -1058,7 +952,7 @@ static const size_t kSmallAnalyze = kStageMin;
 // spectrum of the last row of the call that just ran on `s` by `route` -> p->d_prev (float64 [N2][2])
 static int carry_spectrum(pvx_plan* p, Route route, int64_t rows_in_call, hipStream_t s) {
     const SpecRow r = spec_row_at(p, route, rows_in_call - 1);
-    return pvx_launch_spec_to_prev(p->d_prev, r.d, 2 * p->N2, r.f32, s);
+    return pvx_launch_spec_to_prev(p->d_prev.as<double>(), r.d, 2 * p->N2, r.f32, s);
 }
 
 // The host entry point of run_pv (PV.py:213-264).
@@ -1089,10 +983,10 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
     size_t limit = (size_t)2 << 30;                                   // per buffer (input chunk + its result block)
     if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
     if (keep) {
-        if ((rc = grow_dev(&p->d_res, &p->res_cap, (size_t)nsig * F * per_frame_out)) != PVX_OK) return rc;
+        if ((rc = p->d_res.grow((size_t)nsig * F * per_frame_out, Sizing::headroom)) != PVX_OK) return rc;
     }
-    if (!p->d_prev) PVX_HIP_CHECK(hipMalloc((void**)&p->d_prev, sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1)));
-    if (prev0) PVX_HIP_CHECK(hipMemcpyAsync(p->d_prev, prev0, sizeof(double) * 2 * p->N2, hipMemcpyHostToDevice, s));
+    if (!p->d_prev && (rc = p->d_prev.alloc(sizeof(double) * 2 * (size_t)(p->N2 > 0 ? p->N2 : 1))) != PVX_OK) return rc;
+    if (prev0) PVX_HIP_CHECK(hipMemcpyAsync(p->d_prev.as<double>(), prev0, sizeof(double) * 2 * p->N2, hipMemcpyHostToDevice, s));
 
     // ---- chunking: units are frames of the one signal, or whole signals of a batch
     const bool by_frames = nsig == 1;
@@ -1156,7 +1050,7 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
         int64_t u0, u1, c_nsamp, c_nsig, c_frames; size_t in_off, in_bytes;
         chunk_geom(c, u0, u1, in_off, in_bytes, c_nsamp, c_nsig, c_frames);
         PVX_HIP_CHECK(hipEventSynchronize(p->ev_done[c & 1]));
-        const HostOut d = block_ptrs(p->d_out[c & 1], c_frames, K);
+        const HostOut d = block_ptrs(p->d_out[c & 1].as<double>(), c_frames, K);
         const size_t r0 = by_frames ? (size_t)u0 : (size_t)u0 * F;
         const size_t nk = (size_t)c_frames * K * sizeof(double), n1 = (size_t)c_frames * sizeof(double);
         int rcc;
@@ -1167,7 +1061,7 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
         return PVX_OK;
     };
 
-    p->progress_live = true;
+    const ProgressScope live(p);               // (nothing after the loop asks for progress_live)
     int64_t last_rows = 0;
     Route route = Route::none;                 // the last chunk's route and spectrum request
     SpecRequest spec;
@@ -1178,41 +1072,41 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
         chunk_geom(c, u0, u1, in_off, in_bytes, c_nsamp, c_nsig, c_frames);
         if (c >= 2) {
             // chunk c-2 used these buffers: its kernels are done (and its results fetched, below)
-            if ((rc = (int)hipEventSynchronize(p->ev_done[b])) != 0) { pvx_set_error("hipEventSynchronize failed"); p->progress_live = false; return PVX_ERR_HIP; }
+            if ((rc = (int)hipEventSynchronize(p->ev_done[b])) != 0) { pvx_set_error("hipEventSynchronize failed"); return PVX_ERR_HIP; }
         }
-        if ((rc = grow_dev(&p->d_in[b], &p->in_cap[b], in_bytes)) != PVX_OK) { p->progress_live = false; return rc; }
+        if ((rc = p->d_in[b].grow(in_bytes, Sizing::headroom)) != PVX_OK) return rc;
         double* ob = nullptr;
         if (!keep) {
-            if ((rc = grow_dev(&p->d_out[b], &p->out_cap[b], (size_t)c_frames * per_frame_out)) != PVX_OK) { p->progress_live = false; return rc; }
-            ob = p->d_out[b];
+            if ((rc = p->d_out[b].grow((size_t)c_frames * per_frame_out, Sizing::headroom)) != PVX_OK) return rc;
+            ob = p->d_out[b].as<double>();
         }
         if (small) {
-            if ((rc = grow_pin(p, out_off + (keep ? 0 : total_out) + spec_pin)) != PVX_OK) { p->progress_live = false; return rc; }
+            if ((rc = p->h_pin.grow(out_off + (keep ? 0 : total_out) + spec_pin, Sizing::exact)) != PVX_OK) return rc;
             // staged in pieces: the DMA of piece i runs under the host copy of piece i+1
             const size_t nel = in_bytes / es, piece = (size_t)64 << 10;
             for (size_t e0 = 0; e0 < nel; e0 += piece) {
                 const size_t cnt = nel - e0 < piece ? nel - e0 : piece;
                 if (narrow) {
-                    narrow_f64_f32((const double*)x + e0, (float*)p->h_pin + e0, cnt);
+                    narrow_f64_f32((const double*)x + e0, p->h_pin.as<float>() + e0, cnt);
                     tr.mark("  piece narrowed");
                 } else {
-                    memcpy((char*)p->h_pin + e0 * es, (const char*)x + e0 * es, cnt * es);
+                    memcpy(p->h_pin.as<char>() + e0 * es, (const char*)x + e0 * es, cnt * es);
                 }
-                PVX_HIP_CHECK(hipMemcpyAsync((char*)p->d_in[b] + e0 * des, (char*)p->h_pin + e0 * des, cnt * des, hipMemcpyHostToDevice, s));
+                PVX_HIP_CHECK(hipMemcpyAsync(p->d_in[b].as<char>() + e0 * des, p->h_pin.as<char>() + e0 * des, cnt * des, hipMemcpyHostToDevice, s));
             }
         } else {
             // pageable: concurrent with the kernels of chunk c-1 on the plan's stream; large chunks through the threaded ring
             const bool threaded = getenv("PVX_NO_STAGE_THREADS") == nullptr;
             if (narrow || (threaded && in_bytes >= kStageMin)) {
-                if ((rc = staged_copy(p, p->d_in[b], (void*)((const char*)x + in_off), narrow ? in_bytes / 2 : in_bytes, true, s, narrow)) != PVX_OK) { p->progress_live = false; return rc; }
+                if ((rc = staged_copy(p, p->d_in[b].get(), (void*)((const char*)x + in_off), narrow ? in_bytes / 2 : in_bytes, true, s, narrow)) != PVX_OK) return rc;
             } else {
-                if ((rc = host_to_device(p->d_in[b], (const char*)x + in_off, in_bytes)) != PVX_OK) { p->progress_live = false; return rc; }
+                if ((rc = host_to_device(p->d_in[b].get(), (const char*)x + in_off, in_bytes)) != PVX_OK) return rc;
             }
         }
         tr.mark("staged + H2D issued");
         HostOut d;
         if (keep) {
-            const HostOut all = block_ptrs(p->d_res, nsig * F, K);
+            const HostOut all = block_ptrs(p->d_res.as<double>(), nsig * F, K);
             const size_t r0 = by_frames ? (size_t)u0 : (size_t)u0 * F;
             d.f = all.f + r0 * K; d.mag = all.mag + r0 * K; d.ph = all.ph + r0 * K; d.realph = all.realph + r0 * K;
             d.binno = all.binno + r0 * K; d.t = nchunks == 1 ? all.t : nullptr; d.totalmag = all.totalmag + r0;
@@ -1220,37 +1114,36 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
             d = block_ptrs(ob, c_frames, K);
             d.t = nullptr;
         }
-        const double* dprev = (c > 0 && by_frames) || prev0 ? p->d_prev : nullptr;
+        const double* dprev = (c > 0 && by_frames) || prev0 ? p->d_prev.as<double>() : nullptr;
         last_rows = c_nsig * (c_frames / c_nsig + 1);
         route = route_for(p, dev_dtype, last_rows);
         spec = SpecRequest{(c + 1 < nchunks && by_frames) || (last_spec && c + 1 == nchunks) ? last_rows - 1 : -1};
         // small call, fused kernels: the last spectrum is written by the kernel itself into the pinned block (one
         // 16 KB burst over PCIe instead of a separate copy operation behind the kernel)
-        if (small && last_spec && is_fused(route) && spec_off + (size_t)p->N2 * 8 <= p->pin_cap) spec.host = (float*)((unsigned char*)p->h_pin + spec_off);
-        rc = analyze_rows(p, route, p->d_in[b], dev_dtype, c_nsamp, c_nsig, by_frames ? c_nsamp : sig_stride, c_frames / c_nsig,
+        if (small && last_spec && is_fused(route) && spec_off + (size_t)p->N2 * 8 <= p->h_pin.cap()) spec.host = (float*)(p->h_pin.as<unsigned char>() + spec_off);
+        rc = analyze_rows(p, route, p->d_in[b].get(), dev_dtype, c_nsamp, c_nsig, by_frames ? c_nsamp : sig_stride, c_frames / c_nsig,
                           d.f, d.mag, d.ph, d.realph, d.binno, d.t, d.totalmag, dprev, s, spec);
         tr.mark("kernels issued");
         if (rc == PVX_OK && c + 1 < nchunks && by_frames) rc = carry_spectrum(p, route, last_rows, s);
-        if (rc != PVX_OK) { p->progress_live = false; return rc; }
+        if (rc != PVX_OK) return rc;
         PVX_HIP_CHECK(hipEventRecord(p->ev_done[b], s));
         if (!keep && !small && c >= 1) {
-            if ((rc = fetch(c - 1)) != PVX_OK) { p->progress_live = false; return rc; }      // under the kernels of chunk c
+            if ((rc = fetch(c - 1)) != PVX_OK) return rc;      // under the kernels of chunk c
         }
         if (p->progress_fn && nchunks > 1 && c + 1 < nchunks) {
             const int64_t done = by_frames ? u1 : u1 * F;
             p->progress_fn(done, nsig * F, p->progress_user);
         }
     }
-    p->progress_live = false;
     // ---- tail: last chunk's results, frame times, the last spectrum
     if (keep) {
-        const HostOut all = block_ptrs(p->d_res, nsig * F, K);
+        const HostOut all = block_ptrs(p->d_res.as<double>(), nsig * F, K);
         if (nchunks > 1 && (rc = pvx_launch_fill_t(all.t, F, nsig, p->hop, p->nfft, p->sr, s)) != PVX_OK) return rc;   // else the kernels wrote it
         p->res_F = F; p->res_nsig = nsig; p->res_valid = true;
     } else if (small) {
         // one D2H of the whole block into pinned memory, one synchronisation, then plain memcpys
-        double* hb = (double*)((char*)p->h_pin + out_off);
-        PVX_HIP_CHECK(hipMemcpyAsync(hb, p->d_out[0], total_out, hipMemcpyDeviceToHost, s));
+        double* hb = (double*)(p->h_pin.as<char>() + out_off);
+        PVX_HIP_CHECK(hipMemcpyAsync(hb, p->d_out[0].as<double>(), total_out, hipMemcpyDeviceToHost, s));
         PVX_HIP_CHECK(hipStreamSynchronize(s));
         const HostOut h = block_ptrs(hb, nsig * F, K);
         const size_t nk = (size_t)nsig * F * K * sizeof(double), n1 = (size_t)nsig * F * sizeof(double);
@@ -1269,8 +1162,8 @@ static int64_t analyze_host(pvx_plan* p, const void* x, int x_dtype, int64_t nsa
     const SpecRow last = last_spec ? spec_row_at(p, route, last_rows - 1) : SpecRow{nullptr, false};
     const size_t last_bytes = (size_t)p->N2 * 2 * (last.f32 ? 4 : 8);
     unsigned char* h_last = (unsigned char*)spec.host;
-    if (last_spec && small && !h_last && spec_off + last_bytes <= p->pin_cap) {
-        h_last = (unsigned char*)p->h_pin + spec_off;
+    if (last_spec && small && !h_last && spec_off + last_bytes <= p->h_pin.cap()) {
+        h_last = p->h_pin.as<unsigned char>() + spec_off;
         PVX_HIP_CHECK(hipMemcpyAsync(h_last, last.d, last_bytes, hipMemcpyDeviceToHost, s));
     }
     tr.mark("tail issued");
@@ -1351,7 +1244,7 @@ extern "C" int pvx_batch_destroy(pvx_batch* b) {
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
     for (size_t i = 0; i < b->plans.size(); i++)
-        if (b->plans[i]) { (void)hipSetDevice(b->devices[i / b->workers]); plan_free(b->plans[i]); }
+        if (b->plans[i]) { (void)hipSetDevice(b->devices[i / b->workers]); delete b->plans[i]; }
     if (have) (void)hipSetDevice(cur);
     delete b;
     return PVX_OK;
@@ -1464,7 +1357,7 @@ extern "C" int pvx_resident_fetch(pvx_plan* p, int which, double* host) {
     if (rc != PVX_OK) return rc;
     if (!host || which < 0 || which > 6) { pvx_set_error("bad fetch argument"); return PVX_ERR_INVALID; }
     const int64_t rows = p->res_nsig * p->res_F;
-    const HostOut all = block_ptrs(p->d_res, rows, p->npks);
+    const HostOut all = block_ptrs(p->d_res.as<double>(), rows, p->npks);
     const double* src[7] = {all.f, all.mag, all.ph, all.realph, all.binno, all.t, all.totalmag};
     const size_t bytes = (size_t)rows * (which < 5 ? p->npks : 1) * sizeof(double);
     PVX_HIP_CHECK(hipStreamSynchronize(p->s_host));
@@ -1473,7 +1366,7 @@ extern "C" int pvx_resident_fetch(pvx_plan* p, int which, double* host) {
 
 extern "C" const double* pvx_resident_ptr(pvx_plan* p, int which) {
     if (!p || !p->res_valid || which < 0 || which > 6) return nullptr;
-    const HostOut all = block_ptrs(p->d_res, p->res_nsig * p->res_F, p->npks);
+    const HostOut all = block_ptrs(p->d_res.as<double>(), p->res_nsig * p->res_F, p->npks);
     const double* src[7] = {all.f, all.mag, all.ph, all.realph, all.binno, all.t, all.totalmag};
     return src[which];
 }
@@ -1490,25 +1383,22 @@ extern "C" int pvx_stft_frames(pvx_plan* p, const void* x, int x_dtype, int64_t 
         if (pos[i] < 0 || pos[i] + p->nfft > nsamp) { pvx_set_error("frame %lld at %lld leaves the signal", (long long)i, (long long)pos[i]); return PVX_ERR_INVALID; }
     // Each requested frame is framed as its own 1-frame "signal" (stride = its position), so the
     // regular framing kernel can be used: signal b = samples [pos[b], pos[b]+nfft+1).
-    DevBuf dx;
+    DevMem dx;
     if ((rc = dx.alloc((size_t)(p->nfft + 1) * es)) != PVX_OK) return rc;
     const int nb = p->nfft / 2 + 1;
     std::vector<unsigned char> row((size_t)nb * 2 * rs);
-    PVX_FFT_CHECK(rocfft_execution_info_set_stream(p->info, nullptr));
     for (int64_t i = 0; i < nfr; i++) {
         // copy nfft samples (+1 so that nframes(nfft+1) == 1)
-        PVX_HIP_CHECK(hipMemset(dx.p, 0, (size_t)(p->nfft + 1) * es));
-        PVX_HIP_CHECK(hipMemcpy(dx.p, (const char*)x + (size_t)pos[i] * es, (size_t)p->nfft * es, hipMemcpyHostToDevice));
+        PVX_HIP_CHECK(hipMemset(dx.get(), 0, (size_t)(p->nfft + 1) * es));
+        PVX_HIP_CHECK(hipMemcpy(dx.get(), (const char*)x + (size_t)pos[i] * es, (size_t)p->nfft * es, hipMemcpyHostToDevice));
         FrameParams fp;
-        fp.x = dx.p; fp.nsamp = p->nfft + 1; fp.sig_stride = p->nfft + 1; fp.F = 1; fp.R0 = 0; fp.ws_rows = 3;
-        fp.total_rows = 2; fp.nfft = p->nfft; fp.hop = p->hop; fp.win = p->d_win; fp.frames = p->d_frames; fp.ldi = p->ldi;
+        fp.x = dx.get(); fp.nsamp = p->nfft + 1; fp.sig_stride = p->nfft + 1; fp.F = 1; fp.R0 = 0; fp.ws_rows = 3;
+        fp.total_rows = 2; fp.nfft = p->nfft; fp.hop = p->hop; fp.win = p->d_win.get(); fp.frames = p->d_frames.get(); fp.ldi = p->ldi;
         if (p->rocfft_rows < 2) { pvx_set_error("plan workspace too small"); return PVX_ERR_SIZE; }
         rc = pvx_launch_frames(fp, x_dtype, p->precision, nullptr);
         if (rc != PVX_OK) return rc;
-        void* rspec = p->rocfft_small ? p->d_rspec : p->d_spec;
-        void* in[1] = {p->d_frames};
-        void* out[1] = {rspec};
-        PVX_FFT_CHECK(rocfft_execute(p->fft, in, out, p->info));
+        void* rspec = p->rocfft_small ? p->d_rspec.get() : p->d_spec.get();
+        PVX_FFT_CHECK(p->fft.execute(p->d_frames.get(), rspec, nullptr));
         PVX_HIP_CHECK(hipStreamSynchronize(nullptr));
         // global row 1 (frame 0) sits in workspace row 2
         PVX_HIP_CHECK(hipMemcpy(row.data(), (char*)rspec + (size_t)2 * p->ldo * 2 * rs, row.size(), hipMemcpyDeviceToHost));
@@ -1529,23 +1419,23 @@ extern "C" int pvx_peakfinder(const double* y, int64_t nrows, int n, int npeaks,
         return PVX_ERR_INVALID;
     }
     if (nrows == 0) return PVX_OK;
-    DevBuf dy, dpos, dkeep, dcount;
+    DevMem dy, dpos, dkeep, dcount;
     const size_t yb = (size_t)nrows * n * sizeof(double);
     if ((rc = dy.alloc(yb)) != PVX_OK || (rc = dpos.alloc((size_t)nrows * cap * 4)) != PVX_OK ||
         (rc = dkeep.alloc((size_t)nrows * cap)) != PVX_OK || (rc = dcount.alloc((size_t)nrows * 4)) != PVX_OK)
         return rc;
-    if ((rc = host_to_device(dy.p, y, yb)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipMemset(dpos.p, 0xff, (size_t)nrows * cap * 4));
-    PVX_HIP_CHECK(hipMemset(dkeep.p, 0, (size_t)nrows * cap));
+    if ((rc = host_to_device(dy.get(), y, yb)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemset(dpos.get(), 0xff, (size_t)nrows * cap * 4));
+    PVX_HIP_CHECK(hipMemset(dkeep.get(), 0, (size_t)nrows * cap));
     PeakRowsParams pp;
-    pp.y = (const double*)dy.p; pp.nrows = nrows; pp.n = n; pp.npeaks = npeaks; pp.thr_kind = thr_kind;
+    pp.y = dy.as<const double>(); pp.nrows = nrows; pp.n = n; pp.npeaks = npeaks; pp.thr_kind = thr_kind;
     pp.thr_val = thr_val; pp.rad = rad; pp.cap = cap;
-    pp.pos = (int32_t*)dpos.p; pp.keep = (int8_t*)dkeep.p; pp.count = (int32_t*)dcount.p;
+    pp.pos = dpos.as<int32_t>(); pp.keep = dkeep.as<int8_t>(); pp.count = dcount.as<int32_t>();
     rc = pvx_launch_peak_rows(pp, nullptr);
     if (rc != PVX_OK) return rc;
     PVX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    if ((rc = device_to_host(pos, dpos.p, (size_t)nrows * cap * 4)) != PVX_OK || (rc = device_to_host(keep, dkeep.p, (size_t)nrows * cap)) != PVX_OK ||
-        (rc = device_to_host(count, dcount.p, (size_t)nrows * 4)) != PVX_OK) return rc;
+    if ((rc = device_to_host(pos, dpos.get(), (size_t)nrows * cap * 4)) != PVX_OK || (rc = device_to_host(keep, dkeep.get(), (size_t)nrows * cap)) != PVX_OK ||
+        (rc = device_to_host(count, dcount.get(), (size_t)nrows * 4)) != PVX_OK) return rc;
     return PVX_OK;
 }
 
@@ -1634,19 +1524,17 @@ extern "C" int64_t pvx_track_dev(const double* d_f, const double* d_mag, int64_t
     // synchronous, one at a time through it
     // (one workspace per DEVICE: a thread bound to another device must not hand its kernels a buffer of this one; the result
     // words are page-locked memory every device can write: hipHostMallocPortable)
-    struct DevWs { char* ws = nullptr; size_t cap = 0; };
     static std::mutex mu;
-    static std::map<int, DevWs> wsd;
+    static std::map<int, DevMem*> wsd;      // (for the process: never deleted, pvx_mem.h)
     static int64_t* pin3 = nullptr;         // { partials, exact double tie, last frame with a point } in page-locked memory:
     std::lock_guard<std::mutex> lk(mu);     // the kernel's three stores are what the host waits for, no copy behind them
     if (!pin3 && hipHostMalloc((void**)&pin3, 64, hipHostMallocPortable) != hipSuccess) { pin3 = nullptr; (void)hipGetLastError(); }
     int dev = 0;
     PVX_HIP_CHECK(hipGetDevice(&dev));
-    DevWs* wp = nullptr;
-    try { wp = &wsd[dev]; } catch (...) { pvx_set_error("out of memory for the tracker's per-device workspace record"); return PVX_ERR_ALLOC; }   // (no C++ exception leaves the C ABI)
-    DevWs& w = *wp;
-    if ((rc = grow_dev(&w.ws, &w.cap, track_ws_bytes(F, K))) != PVX_OK) return rc;
-    return track_on(d_f, d_mag, F, K, maxpitchjmp, d_partial_id, d_part_start, d_part_len, cap, w.ws, (hipStream_t)stream, nullptr, pin3);
+    DevMem* w = nullptr;
+    try { DevMem*& e = wsd[dev]; if (!e) e = new DevMem(); w = e; } catch (...) { pvx_set_error("out of memory for the tracker's per-device workspace record"); return PVX_ERR_ALLOC; }   // (no C++ exception leaves the C ABI)
+    if ((rc = w->grow(track_ws_bytes(F, K), Sizing::headroom)) != PVX_OK) return rc;
+    return track_on(d_f, d_mag, F, K, maxpitchjmp, d_partial_id, d_part_start, d_part_len, cap, w->as<char>(), (hipStream_t)stream, nullptr, pin3);
 }
 
 extern "C" int pvx_synth_dev_flags(const double* d_f, const double* d_mag, const double* d_realph, const int32_t* d_partial_id,
@@ -1671,21 +1559,19 @@ extern "C" int64_t pvx_track_resident(pvx_plan* p, double maxpitchjmp, int64_t* 
     const int K = p->npks;
     const size_t n = (size_t)F * K;
     if (n > p->trk_cap) {
-        if (p->d_pid) (void)hipFree(p->d_pid);
-        if (p->d_pst) (void)hipFree(p->d_pst);
-        if (p->d_pln) (void)hipFree(p->d_pln);
-        p->d_pid = p->d_pst = p->d_pln = nullptr; p->trk_cap = 0;
-        if (hipMalloc((void**)&p->d_pid, n * 4) != hipSuccess || hipMalloc((void**)&p->d_pst, n * 4) != hipSuccess ||
-            hipMalloc((void**)&p->d_pln, n * 4) != hipSuccess) { pvx_set_error("hipMalloc of the partial table failed"); return PVX_ERR_ALLOC; }
+        p->d_pid.reset(); p->d_pst.reset(); p->d_pln.reset(); p->trk_cap = 0;
+        if (p->d_pid.alloc(n * 4) != PVX_OK || p->d_pst.alloc(n * 4) != PVX_OK || p->d_pln.alloc(n * 4) != PVX_OK) {
+            pvx_set_error("hipMalloc of the partial table failed"); return PVX_ERR_ALLOC;
+        }
         p->trk_cap = n;
     }
-    if ((rc = grow_dev(&p->d_tws, &p->tws_cap, track_ws_bytes(F, K))) != PVX_OK) return rc;
-    const HostOut all = block_ptrs(p->d_res, F, K);
+    if ((rc = p->d_tws.grow(track_ws_bytes(F, K), Sizing::headroom)) != PVX_OK) return rc;
+    const HostOut all = block_ptrs(p->d_res.as<double>(), F, K);
     int64_t maxend = -1;
-    if ((rc = grow_pin(p, 64)) != PVX_OK) return rc;
+    if ((rc = p->h_pin.grow(64, Sizing::exact)) != PVX_OK) return rc;
     HostTrace tr("track");
-    const int64_t P = track_on(all.f, all.mag, F, K, maxpitchjmp, p->d_pid, p->d_pst, p->d_pln, (int64_t)n, (char*)p->d_tws, p->s_host, &maxend,
-                               (int64_t*)p->h_pin);
+    const int64_t P = track_on(all.f, all.mag, F, K, maxpitchjmp, p->d_pid.as<int32_t>(), p->d_pst.as<int32_t>(), p->d_pln.as<int32_t>(), (int64_t)n, p->d_tws.as<char>(), p->s_host, &maxend,
+                               p->h_pin.as<int64_t>());
     tr.mark("launched + synchronised");
     if (P < 0) return P;
     p->res_P = P; p->res_maxend = maxend;
@@ -1698,9 +1584,9 @@ extern "C" int pvx_resident_fetch_table(pvx_plan* p, int32_t* partial_id, int32_
     if (rc != PVX_OK) return rc;
     if (p->res_P < 0) { pvx_set_error("no resident partial table (pvx_track_resident first)"); return PVX_ERR_INVALID; }
     PVX_HIP_CHECK(hipStreamSynchronize(p->s_host));
-    if (partial_id && (rc = device_to_host(partial_id, p->d_pid, (size_t)p->res_F * p->npks * 4)) != PVX_OK) return rc;
-    if (part_start && p->res_P && (rc = device_to_host(part_start, p->d_pst, (size_t)p->res_P * 4)) != PVX_OK) return rc;
-    if (part_len && p->res_P && (rc = device_to_host(part_len, p->d_pln, (size_t)p->res_P * 4)) != PVX_OK) return rc;
+    if (partial_id && (rc = device_to_host(partial_id, p->d_pid.as<int32_t>(), (size_t)p->res_F * p->npks * 4)) != PVX_OK) return rc;
+    if (part_start && p->res_P && (rc = device_to_host(part_start, p->d_pst.as<int32_t>(), (size_t)p->res_P * 4)) != PVX_OK) return rc;
+    if (part_len && p->res_P && (rc = device_to_host(part_len, p->d_pln.as<int32_t>(), (size_t)p->res_P * 4)) != PVX_OK) return rc;
     return PVX_OK;
 }
 
@@ -1714,12 +1600,13 @@ extern "C" int pvx_synth_resident(pvx_plan* p, double sr, int hop_synth, double 
     if (need < 0 || need != wlen) { pvx_set_error("output length %lld, expected %lld", (long long)wlen, (long long)need); return PVX_ERR_SIZE; }
     HostTrace tr("synth");
     {
-        const void* before = p->d_sws;
-        const size_t cap_before = p->sws_cap;
-        if ((rc = grow_dev(&p->d_sws, &p->sws_cap, pvx_synth_ws_bytes(p->res_F, p->npks, p->res_P, p->nfft, p->hop, hop_synth, edge))) != PVX_OK) return rc;
-        if (p->d_sws != before || p->sws_cap != cap_before) p->sws_gen = 0;           // a new buffer: its flags are cleared on first use
+        const void* before = p->d_sws.get();
+        const size_t cap_before = p->d_sws.cap();
+        if ((rc = p->d_sws.grow(pvx_synth_ws_bytes(p->res_F, p->npks, p->res_P, p->nfft, p->hop, hop_synth, edge), Sizing::headroom)) != PVX_OK) return rc;
+        if (p->d_sws.get() != before || p->d_sws.cap() != cap_before) p->sws_gen = 0;           // a new buffer: its flags are cleared on first use
     }
-    const HostOut all = block_ptrs(p->d_res, p->res_F, p->npks);
+    const HostOut all = block_ptrs(p->d_res.as<double>(), p->res_F, p->npks);
+    const int32_t *pid = p->d_pid.as<int32_t>(), *pst = p->d_pst.as<int32_t>(), *pln = p->d_pln.as<int32_t>();
     const size_t bytes = (size_t)wlen * 8;
     hipPointerAttribute_t attr;
     const bool pinned = hipPointerGetAttributes(&attr, w) == hipSuccess && attr.type == hipMemoryTypeHost;
@@ -1731,33 +1618,33 @@ extern "C" int pvx_synth_resident(pvx_plan* p, double sr, int hop_synth, double 
         // the caller's array is page-locked (pvx_host_alloc) and small: the kernel stores its segments straight into
         // it (posted writes over PCIe, spread over the kernel's run time as workgroups finish) -- no copy operation
         // behind the kernel at all
-        rc = synth_slice(all.f, all.mag, all.realph, p->d_pid, p->res_F, p->npks, p->d_pst, p->d_pln, p->res_P, sr, p->nfft,
-                         p->hop, hop_synth, edge, minframes, w, wlen, p->s_host, 0, 0, true, p->d_sws, p->sws_cap, &p->sws_gen, plan_synth_f32(p));
+        rc = synth_slice(all.f, all.mag, all.realph, pid, p->res_F, p->npks, pst, pln, p->res_P, sr, p->nfft,
+                         p->hop, hop_synth, edge, minframes, w, wlen, p->s_host, 0, 0, true, p->d_sws.get(), p->d_sws.cap(), &p->sws_gen, plan_synth_f32(p));
         if (rc != PVX_OK) return rc;
         tr.mark("kernel issued");
         PVX_HIP_CHECK(hipStreamSynchronize(p->s_host));
         tr.mark("here");
         return PVX_OK;
     }
-    if ((rc = grow_dev(&p->d_w, &p->w_cap, (size_t)wlen * 8)) != PVX_OK) return rc;
+    if ((rc = p->d_w.grow((size_t)wlen * 8, Sizing::headroom)) != PVX_OK) return rc;
     if (pinned && bytes >= kStageMin && getenv("PVX_NO_SYNTH_SLICES") == nullptr) {
         // a large waveform into page-locked memory: the segments are computed in slices and the DMA of a finished slice
         // (second stream) runs under the next slice's kernel -- the link, not kernel + link, is what the call costs
         if ((rc = stage_ring(p)) != PVX_OK) return rc;                   // (its events)
-        if (!p->s_copy) PVX_HIP_CHECK(hipStreamCreateWithFlags(&p->s_copy, hipStreamNonBlocking));
+        PVX_HIP_CHECK(p->s_copy.ensure(hipStreamNonBlocking));
         const int NS = 8;                                                // slices (ev_ring holds 16 events)
         const int64_t nseg = (wlen + hop_synth - 1) / hop_synth, per = (nseg + NS - 1) / NS;
         for (int i = 0; i < NS; i++) {
             const int64_t s0 = (int64_t)i * per;
             if (s0 >= nseg) break;
             const int64_t cnt = nseg - s0 < per ? nseg - s0 : per;
-            rc = synth_slice(all.f, all.mag, all.realph, p->d_pid, p->res_F, p->npks, p->d_pst, p->d_pln, p->res_P, sr, p->nfft, p->hop, hop_synth,
-                             edge, minframes, p->d_w, wlen, p->s_host, s0, cnt, i == 0, p->d_sws, p->sws_cap, &p->sws_gen, plan_synth_f32(p));
+            rc = synth_slice(all.f, all.mag, all.realph, pid, p->res_F, p->npks, pst, pln, p->res_P, sr, p->nfft, p->hop, hop_synth,
+                             edge, minframes, p->d_w.as<double>(), wlen, p->s_host, s0, cnt, i == 0, p->d_sws.get(), p->d_sws.cap(), &p->sws_gen, plan_synth_f32(p));
             if (rc != PVX_OK) return rc;
             PVX_HIP_CHECK(hipEventRecord(p->ev_ring[i], p->s_host));
             PVX_HIP_CHECK(hipStreamWaitEvent(p->s_copy, p->ev_ring[i], 0));
             const int64_t o = s0 * hop_synth, c = (wlen - o < cnt * hop_synth) ? wlen - o : cnt * hop_synth;
-            PVX_HIP_CHECK(hipMemcpyAsync(w + o, p->d_w + o, (size_t)c * 8, hipMemcpyDeviceToHost, p->s_copy));
+            PVX_HIP_CHECK(hipMemcpyAsync(w + o, p->d_w.as<double>() + o, (size_t)c * 8, hipMemcpyDeviceToHost, p->s_copy));
         }
         tr.mark("slices + copies issued");
         PVX_HIP_CHECK(hipStreamSynchronize(p->s_copy));
@@ -1765,12 +1652,12 @@ extern "C" int pvx_synth_resident(pvx_plan* p, double sr, int hop_synth, double 
         tr.mark("here");
         return PVX_OK;
     }
-    rc = synth_slice(all.f, all.mag, all.realph, p->d_pid, p->res_F, p->npks, p->d_pst, p->d_pln, p->res_P, sr, p->nfft,
-                     p->hop, hop_synth, edge, minframes, p->d_w, wlen, p->s_host, 0, 0, true, p->d_sws, p->sws_cap, &p->sws_gen, plan_synth_f32(p));
+    rc = synth_slice(all.f, all.mag, all.realph, pid, p->res_F, p->npks, pst, pln, p->res_P, sr, p->nfft,
+                     p->hop, hop_synth, edge, minframes, p->d_w.as<double>(), wlen, p->s_host, 0, 0, true, p->d_sws.get(), p->d_sws.cap(), &p->sws_gen, plan_synth_f32(p));
     if (rc != PVX_OK) return rc;
     if (pinned) {
         // the caller's array is page-locked: the DMA lands in it, nothing to stage or copy
-        PVX_HIP_CHECK(hipMemcpyAsync(w, p->d_w, bytes, hipMemcpyDeviceToHost, p->s_host));
+        PVX_HIP_CHECK(hipMemcpyAsync(w, p->d_w.as<double>(), bytes, hipMemcpyDeviceToHost, p->s_host));
         tr.mark("kernel + copy issued");
         PVX_HIP_CHECK(hipStreamSynchronize(p->s_host));
         tr.mark("here");
@@ -1778,12 +1665,12 @@ extern "C" int pvx_synth_resident(pvx_plan* p, double sr, int hop_synth, double 
     }
     if (bytes <= kSmallCall) {
         // through pinned memory in pieces: the host copy of piece i runs under the DMA of piece i+1 (two events in turn)
-        if ((rc = grow_pin(p, bytes)) != PVX_OK) return rc;
+        if ((rc = p->h_pin.grow(bytes, Sizing::exact)) != PVX_OK) return rc;
         const size_t piece = bytes > ((size_t)256 << 10) ? ((bytes + 3) / 4 + 255) & ~(size_t)255 : bytes;
         const int np_ = (int)((bytes + piece - 1) / piece);
         auto issue = [&](int i) -> int {
             const size_t o = (size_t)i * piece, c = bytes - o < piece ? bytes - o : piece;
-            PVX_HIP_CHECK(hipMemcpyAsync((char*)p->h_pin + o, (const char*)p->d_w + o, c, hipMemcpyDeviceToHost, p->s_host));
+            PVX_HIP_CHECK(hipMemcpyAsync(p->h_pin.as<char>() + o, p->d_w.as<const char>() + o, c, hipMemcpyDeviceToHost, p->s_host));
             PVX_HIP_CHECK(hipEventRecord(p->ev_done[i & 1], p->s_host));
             return PVX_OK;
         };
@@ -1794,18 +1681,18 @@ extern "C" int pvx_synth_resident(pvx_plan* p, double sr, int hop_synth, double 
             const size_t o = (size_t)i * piece, c = bytes - o < piece ? bytes - o : piece;
             PVX_HIP_CHECK(hipEventSynchronize(p->ev_done[i & 1]));
             if (i + 2 < np_ && (rc = issue(i + 2)) != PVX_OK) return rc;       // its event is free again
-            memcpy((char*)w + o, (const char*)p->h_pin + o, c);
+            memcpy((char*)w + o, p->h_pin.as<const char>() + o, c);
         }
         tr.mark("copied out");
     } else {
         const bool threaded = getenv("PVX_NO_STAGE_THREADS") == nullptr;
         if (threaded && bytes >= kStageMin) {
             // (the DMAs are queued behind the kernel on the same stream)
-            if ((rc = staged_copy(p, p->d_w, w, bytes, false, p->s_host)) != PVX_OK) return rc;
+            if ((rc = staged_copy(p, p->d_w.as<double>(), w, bytes, false, p->s_host)) != PVX_OK) return rc;
             tr.mark("copied out (threaded ring)");
         } else {
             PVX_HIP_CHECK(hipStreamSynchronize(p->s_host));
-            if ((rc = device_to_host(w, p->d_w, bytes)) != PVX_OK) return rc;
+            if ((rc = device_to_host(w, p->d_w.as<double>(), bytes)) != PVX_OK) return rc;
         }
     }
     return PVX_OK;
@@ -1817,9 +1704,9 @@ extern "C" int pvx_f0_resident(pvx_plan* p, double fmin, double fmax, double thr
     if (rc != PVX_OK) return rc;
     if (!fm || !idx) { pvx_set_error("null output array"); return PVX_ERR_INVALID; }
     const int64_t rows = p->res_nsig * p->res_F;
-    if ((rc = grow_dev(&p->d_desc, &p->desc_cap, (size_t)rows * 12)) != PVX_OK) return rc;
-    const HostOut all = block_ptrs(p->d_res, rows, p->npks);
-    double* d_fm = (double*)p->d_desc;
+    if ((rc = p->d_desc.grow((size_t)rows * 12, Sizing::headroom)) != PVX_OK) return rc;
+    const HostOut all = block_ptrs(p->d_res.as<double>(), rows, p->npks);
+    double* d_fm = p->d_desc.as<double>();
     int32_t* d_im = (int32_t*)(d_fm + rows);
     if ((rc = pvx_launch_f0(all.f, all.mag, rows, p->npks, fmin, fmax, thr, d_fm, d_im, p->s_host)) != PVX_OK) return rc;
     PVX_HIP_CHECK(hipStreamSynchronize(p->s_host));
@@ -1837,9 +1724,9 @@ extern "C" int pvx_harmonic_power_resident(pvx_plan* p, double f_threshold, doub
     const int64_t F = p->res_F;
     const int K = p->npks;
     const size_t n = (size_t)F * K;
-    if ((rc = grow_dev(&p->d_desc, &p->desc_cap, n * 16 + (size_t)K * 8 + 16)) != PVX_OK) return rc;
-    const HostOut all = block_ptrs(p->d_res, F, K);
-    double* d_hp = (double*)p->d_desc;
+    if ((rc = p->d_desc.grow(n * 16 + (size_t)K * 8 + 16, Sizing::headroom)) != PVX_OK) return rc;
+    const HostOut all = block_ptrs(p->d_res.as<double>(), F, K);
+    double* d_hp = p->d_desc.as<double>();
     double* d_nh = d_hp + n;
     double* d_rp = d_nh + n;
     int32_t* d_top = (int32_t*)(d_rp + K);
@@ -1863,17 +1750,17 @@ extern "C" int64_t pvx_track(const double* f, const double* mag, int64_t F, int 
     if (!f || !mag || !partial_id || !part_start || !part_len) { pvx_set_error("null tracker array"); return PVX_ERR_INVALID; }
     const size_t n = (size_t)F * K;
     const int64_t dcap = (int64_t)n;           // always sufficient on the device side
-    DevBuf df, dm, dpid, dst, dln;
+    DevMem df, dm, dpid, dst, dln;
     if ((rc = df.alloc(n * 8)) != PVX_OK || (rc = dm.alloc(n * 8)) != PVX_OK || (rc = dpid.alloc(n * 4)) != PVX_OK ||
         (rc = dst.alloc(n * 4)) != PVX_OK || (rc = dln.alloc(n * 4)) != PVX_OK)
         return rc;
-    if ((rc = host_to_device(df.p, f, n * 8)) != PVX_OK || (rc = host_to_device(dm.p, mag, n * 8)) != PVX_OK) return rc;
-    const int64_t P = pvx_track_dev((const double*)df.p, (const double*)dm.p, F, K, maxpitchjmp, (int32_t*)dpid.p,
-                                    (int32_t*)dst.p, (int32_t*)dln.p, dcap, nullptr);
+    if ((rc = host_to_device(df.get(), f, n * 8)) != PVX_OK || (rc = host_to_device(dm.get(), mag, n * 8)) != PVX_OK) return rc;
+    const int64_t P = pvx_track_dev(df.as<const double>(), dm.as<const double>(), F, K, maxpitchjmp, dpid.as<int32_t>(),
+                                    dst.as<int32_t>(), dln.as<int32_t>(), dcap, nullptr);
     if (P < 0) return P;
     if (P > cap) { pvx_set_error("%lld partials exceed the caller's capacity %lld", (long long)P, (long long)cap); return PVX_ERR_SIZE; }
-    if ((rc = device_to_host(partial_id, dpid.p, n * 4)) != PVX_OK || (rc = device_to_host(part_start, dst.p, (size_t)P * 4)) != PVX_OK ||
-        (rc = device_to_host(part_len, dln.p, (size_t)P * 4)) != PVX_OK) return rc;
+    if ((rc = device_to_host(partial_id, dpid.get(), n * 4)) != PVX_OK || (rc = device_to_host(part_start, dst.get(), (size_t)P * 4)) != PVX_OK ||
+        (rc = device_to_host(part_len, dln.get(), (size_t)P * 4)) != PVX_OK) return rc;
     return P;
 }
 
@@ -1903,17 +1790,15 @@ static int harmonic_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsam
     }
     *any_valid = last >= 0;
     if (F > p->harm_cap) {
-        if (p->d_hf0) (void)hipFree(p->d_hf0);
-        if (p->d_hprev) (void)hipFree(p->d_hprev);
-        p->d_hf0 = nullptr; p->d_hprev = nullptr; p->harm_cap = 0;
-        if (hipMalloc((void**)&p->d_hf0, (size_t)F * 8) != hipSuccess || hipMalloc((void**)&p->d_hprev, (size_t)F * 4) != hipSuccess) {
+        p->d_hf0.reset(); p->d_hprev.reset(); p->harm_cap = 0;
+        if (p->d_hf0.alloc((size_t)F * 8) != PVX_OK || p->d_hprev.alloc((size_t)F * 4) != PVX_OK) {
             pvx_set_error("hipMalloc of the f0 tables failed"); return PVX_ERR_ALLOC;
         }
         p->harm_cap = F;
     }
-    if (!p->d_carry && hipMalloc(&p->d_carry, (size_t)p->ldo * 2 * rs) != hipSuccess) { pvx_set_error("hipMalloc(carry) failed"); return PVX_ERR_ALLOC; }
-    PVX_HIP_CHECK(hipMemcpyAsync(p->d_hf0, f0, (size_t)F * 8, hipMemcpyHostToDevice, s));
-    PVX_HIP_CHECK(hipMemcpyAsync(p->d_hprev, prow.data(), (size_t)F * 4, hipMemcpyHostToDevice, s));
+    if (!p->d_carry && p->d_carry.alloc((size_t)p->ldo * 2 * rs) != PVX_OK) { pvx_set_error("hipMalloc(carry) failed"); return PVX_ERR_ALLOC; }
+    PVX_HIP_CHECK(hipMemcpyAsync(p->d_hf0.as<double>(), f0, (size_t)F * 8, hipMemcpyHostToDevice, s));
+    PVX_HIP_CHECK(hipMemcpyAsync(p->d_hprev.as<int32_t>(), prow.data(), (size_t)F * 4, hipMemcpyHostToDevice, s));
     PVX_HIP_CHECK(hipStreamSynchronize(s));                              // prow is a local
     const int64_t total_rows = F + 1;
     for (int64_t R0 = 0; R0 < total_rows; R0 += p->max_rows) {
@@ -1921,25 +1806,25 @@ static int harmonic_rows(pvx_plan* p, const void* d_x, int x_dtype, int64_t nsam
         FrameParams fp;
         fp.x = d_x; fp.nsamp = nsamp; fp.sig_stride = nsamp; fp.F = F; fp.R0 = R0;
         fp.ws_rows = nrows + 1; fp.total_rows = total_rows; fp.nfft = p->nfft; fp.hop = p->hop;
-        fp.win = p->d_win; fp.frames = p->d_frames; fp.ldi = p->ldi;
+        fp.win = p->d_win.get(); fp.frames = p->d_frames.get(); fp.ldi = p->ldi;
         if ((rc = launch_transform(p, fp, x_dtype, s)) != PVX_OK || (rc = plan_event(p, s, -1)) != PVX_OK) return rc;
         HarmParams hp;
-        hp.spec = p->d_spec; hp.ldo = p->ldo;
+        hp.spec = p->d_spec.get(); hp.ldo = p->ldo;
         hp.fr_begin = (R0 > 1 ? R0 : 1) - 1;
         const int64_t fr_last = R0 + nrows - 2;
         hp.nfr = fr_last - hp.fr_begin + 1;
         hp.ws_off = hp.fr_begin + 1 - R0 + 1;
         hp.nfft = p->nfft; hp.hop = p->hop; hp.N2 = p->N2; hp.K = p->npks;
         hp.sr = p->sr; hp.fstep = p->fstep; hp.dt = p->dt; hp.fmin = fmin;
-        hp.wfbin = p->d_wfbin; hp.prev0 = d_prev0; hp.carry = p->d_carry;
-        hp.f0 = p->d_hf0; hp.prevrow = p->d_hprev;
+        hp.wfbin = p->d_wfbin.as<double>(); hp.prev0 = d_prev0; hp.carry = p->d_carry.get();
+        hp.f0 = p->d_hf0.as<double>(); hp.prevrow = p->d_hprev.as<int32_t>();
         hp.f = d_f; hp.mag = d_mag; hp.ph = d_ph; hp.residual = d_res; hp.t = d_t;
         if ((rc = pvx_launch_harmonic(hp, p->precision, s)) != PVX_OK) return rc;
         // carry the spectrum of the last valid frame of this chunk to the later ones
         int64_t lv = fr_last;
         while (lv >= hp.fr_begin && !(f0[lv] > 0.0)) lv--;
         if (lv >= hp.fr_begin)
-            PVX_HIP_CHECK(hipMemcpyAsync(p->d_carry, (const char*)p->d_spec + (size_t)(lv + 1 - R0 + 1) * p->ldo * 2 * rs,
+            PVX_HIP_CHECK(hipMemcpyAsync(p->d_carry.get(), p->d_spec.as<const char>() + (size_t)(lv + 1 - R0 + 1) * p->ldo * 2 * rs,
                                          (size_t)p->ldo * 2 * rs, hipMemcpyDeviceToDevice, s));
         if ((rc = plan_progress(p, s, R0 + nrows, total_rows, 1)) != PVX_OK) return rc;
     }
@@ -1985,24 +1870,25 @@ extern "C" int64_t pvx_harmonic_analyze(pvx_plan* p, const void* x, int x_dtype,
     const size_t xbytes = (size_t)nsamp * dtype_size(x_dtype);
     const size_t fk = (size_t)F * p->npks * sizeof(double), f1 = (size_t)F * sizeof(double);
     HostTrace tr("harmonic");
-    DevBuf dout, dprev;
-    if ((rc = grow_dev(&p->d_hx, &p->hx_cap, xbytes)) != PVX_OK) return rc;
-    struct { void* p; } dx = {p->d_hx};
+    DevMem dout, dprev;
+    if ((rc = p->d_hx.grow(xbytes, Sizing::headroom)) != PVX_OK) return rc;
+    void* const d_x = p->d_hx.get();
     if ((rc = dout.alloc(3 * fk + 2 * f1)) != PVX_OK) return rc;
     tr.mark("device buffers");
-    if ((rc = host_to_device(dx.p, x, xbytes)) != PVX_OK) return rc;
+    if ((rc = host_to_device(d_x, x, xbytes)) != PVX_OK) return rc;
     tr.mark("signal on the device");
     if (prev0) {
         if ((rc = dprev.alloc(sizeof(double) * 2 * p->N2)) != PVX_OK) return rc;
-        PVX_HIP_CHECK(hipMemcpy(dprev.p, prev0, sizeof(double) * 2 * p->N2, hipMemcpyHostToDevice));
+        PVX_HIP_CHECK(hipMemcpy(dprev.get(), prev0, sizeof(double) * 2 * p->N2, hipMemcpyHostToDevice));
     }
-    char* o = (char*)dout.p;
+    char* o = dout.as<char>();
     double *d_f = (double*)o, *d_mag = (double*)(o + fk), *d_ph = (double*)(o + 2 * fk), *d_res = (double*)(o + 3 * fk),
            *d_t = (double*)(o + 3 * fk + f1);
     bool any = false;
-    p->progress_live = true;
-    rc = harmonic_rows(p, dx.p, x_dtype, nsamp, F, f0, fmin, d_f, d_mag, d_ph, d_res, d_t, (const double*)dprev.p, nullptr, &any);
-    p->progress_live = false;
+    {
+        const ProgressScope live(p);
+        rc = harmonic_rows(p, d_x, x_dtype, nsamp, F, f0, fmin, d_f, d_mag, d_ph, d_res, d_t, dprev.as<const double>(), nullptr, &any);
+    }
     if (rc != PVX_OK) return rc;
     PVX_HIP_CHECK(hipStreamSynchronize(nullptr));
     tr.mark("kernels");
@@ -2015,7 +1901,7 @@ extern "C" int64_t pvx_harmonic_analyze(pvx_plan* p, const void* x, int x_dtype,
         if (any) {
             const size_t rs = real_size(p->precision);
             std::vector<unsigned char> tmp((size_t)p->N2 * 2 * rs);
-            PVX_HIP_CHECK(hipMemcpy(tmp.data(), p->d_carry, tmp.size(), hipMemcpyDeviceToHost));
+            PVX_HIP_CHECK(hipMemcpy(tmp.data(), p->d_carry.get(), tmp.size(), hipMemcpyDeviceToHost));
             for (int i = 0; i < 2 * p->N2; i++)
                 last_spec[i] = p->precision == 32 ? (double)((float*)tmp.data())[i] : ((double*)tmp.data())[i];
         } else {
@@ -2035,6 +1921,19 @@ static int reduce_args(int64_t n, const double* wind, int wlen, int hop, double*
     return PVX_OK;
 }
 
+// what the `_dev` reductions share: the window on the device, the launch on `s`, and the synchronisation after which the
+// window's buffer may go
+template <typename Launch> static int reduce_with_window(ReduceParams& rp, const double* wind, hipStream_t s, Launch launch) {
+    DevMem dw;
+    int rc;
+    if ((rc = dw.alloc((size_t)rp.wlen * 8)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemcpy(dw.get(), wind, (size_t)rp.wlen * 8, hipMemcpyHostToDevice));
+    rp.wind = dw.as<const double>();
+    if ((rc = launch(rp, s)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipStreamSynchronize(s));
+    return PVX_OK;
+}
+
 extern "C" int64_t pvx_heterodyne_dev(const double* d_x, const double* d_hetsig, int64_t n, const double* wind, int wlen, int hop,
                                       double* d_out, int64_t* d_icent, void* stream) {
     int rc = pvx_require_device();
@@ -2044,15 +1943,11 @@ extern "C" int64_t pvx_heterodyne_dev(const double* d_x, const double* d_hetsig,
     const int64_t nfr = pvx_nframes(n, wlen, hop);
     if (nfr == 0) return 0;
     if (!d_x || !d_hetsig || !d_out) { pvx_set_error("null heterodyne array"); return PVX_ERR_INVALID; }
-    DevBuf dw;
-    if ((rc = dw.alloc((size_t)wlen * 8)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipMemcpy(dw.p, wind, (size_t)wlen * 8, hipMemcpyHostToDevice));
     ReduceParams rp = {};
-    rp.x = d_x; rp.hetsig = d_hetsig; rp.wind = (const double*)dw.p; rp.nfr = nfr; rp.wlen = wlen; rp.hop = hop;
+    rp.x = d_x; rp.hetsig = d_hetsig; rp.nfr = nfr; rp.wlen = wlen; rp.hop = hop;
     rp.norm = norm; rp.out = d_out; rp.icent = d_icent;
-    if ((rc = pvx_launch_reduce(rp, 0, (hipStream_t)stream)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));            // dw is a local
-    return nfr;
+    rc = reduce_with_window(rp, wind, (hipStream_t)stream, [](const ReduceParams& q, hipStream_t s) { return pvx_launch_reduce(q, 0, s); });
+    return rc == PVX_OK ? nfr : rc;
 }
 
 extern "C" int64_t pvx_heterodyne(const double* x, const double* hetsig, int64_t n, const double* wind, int wlen, int hop,
@@ -2064,15 +1959,15 @@ extern "C" int64_t pvx_heterodyne(const double* x, const double* hetsig, int64_t
     const int64_t nfr = pvx_nframes(n, wlen, hop);
     if (nfr == 0) return 0;
     if (!x || !hetsig || !out) { pvx_set_error("null heterodyne array"); return PVX_ERR_INVALID; }
-    DevBuf dx, dh, dout, dic;
+    DevMem dx, dh, dout, dic;
     if ((rc = dx.alloc((size_t)n * 8)) != PVX_OK || (rc = dh.alloc((size_t)n * 16)) != PVX_OK ||
         (rc = dout.alloc((size_t)nfr * 16)) != PVX_OK || (rc = dic.alloc((size_t)nfr * 8)) != PVX_OK) return rc;
-    if ((rc = host_to_device(dx.p, x, (size_t)n * 8)) != PVX_OK || (rc = host_to_device(dh.p, hetsig, (size_t)n * 16)) != PVX_OK) return rc;
-    const int64_t r = pvx_heterodyne_dev((const double*)dx.p, (const double*)dh.p, n, wind, wlen, hop, (double*)dout.p,
-                                         (int64_t*)dic.p, nullptr);
+    if ((rc = host_to_device(dx.get(), x, (size_t)n * 8)) != PVX_OK || (rc = host_to_device(dh.get(), hetsig, (size_t)n * 16)) != PVX_OK) return rc;
+    const int64_t r = pvx_heterodyne_dev(dx.as<const double>(), dh.as<const double>(), n, wind, wlen, hop, dout.as<double>(),
+                                         dic.as<int64_t>(), nullptr);
     if (r < 0) return r;
-    if ((rc = device_to_host(out, dout.p, (size_t)nfr * 16)) != PVX_OK) return rc;
-    if (icent && (rc = device_to_host(icent, dic.p, (size_t)nfr * 8)) != PVX_OK) return rc;
+    if ((rc = device_to_host(out, dout.get(), (size_t)nfr * 16)) != PVX_OK) return rc;
+    if (icent && (rc = device_to_host(icent, dic.get(), (size_t)nfr * 8)) != PVX_OK) return rc;
     return nfr;
 }
 
@@ -2085,14 +1980,10 @@ extern "C" int64_t pvx_rms_frames_dev(const double* d_x, int64_t n, const double
     const int64_t nfr = pvx_nframes(n, wlen, hop);
     if (nfr == 0) return 0;
     if (!d_x || !d_out) { pvx_set_error("null rms array"); return PVX_ERR_INVALID; }
-    DevBuf dw;
-    if ((rc = dw.alloc((size_t)wlen * 8)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipMemcpy(dw.p, wind, (size_t)wlen * 8, hipMemcpyHostToDevice));
     ReduceParams rp = {};
-    rp.x = d_x; rp.wind = (const double*)dw.p; rp.nfr = nfr; rp.wlen = wlen; rp.hop = hop; rp.norm = norm; rp.out = d_out;
-    if ((rc = pvx_launch_reduce(rp, 1, (hipStream_t)stream)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    return nfr;
+    rp.x = d_x; rp.nfr = nfr; rp.wlen = wlen; rp.hop = hop; rp.norm = norm; rp.out = d_out;
+    rc = reduce_with_window(rp, wind, (hipStream_t)stream, [](const ReduceParams& q, hipStream_t s) { return pvx_launch_reduce(q, 1, s); });
+    return rc == PVX_OK ? nfr : rc;
 }
 
 extern "C" int64_t pvx_rms_frames(const double* x, int64_t n, const double* wind, int wlen, int hop, double* out) {
@@ -2103,12 +1994,12 @@ extern "C" int64_t pvx_rms_frames(const double* x, int64_t n, const double* wind
     const int64_t nfr = pvx_nframes(n, wlen, hop);
     if (nfr == 0) return 0;
     if (!x || !out) { pvx_set_error("null rms array"); return PVX_ERR_INVALID; }
-    DevBuf dx, dout;
+    DevMem dx, dout;
     if ((rc = dx.alloc((size_t)n * 8)) != PVX_OK || (rc = dout.alloc((size_t)nfr * 8)) != PVX_OK) return rc;
-    if ((rc = host_to_device(dx.p, x, (size_t)n * 8)) != PVX_OK) return rc;
-    const int64_t r = pvx_rms_frames_dev((const double*)dx.p, n, wind, wlen, hop, (double*)dout.p, nullptr);
+    if ((rc = host_to_device(dx.get(), x, (size_t)n * 8)) != PVX_OK) return rc;
+    const int64_t r = pvx_rms_frames_dev(dx.as<const double>(), n, wind, wlen, hop, dout.as<double>(), nullptr);
     if (r < 0) return r;
-    if ((rc = device_to_host(out, dout.p, (size_t)nfr * 8)) != PVX_OK) return rc;
+    if ((rc = device_to_host(out, dout.get(), (size_t)nfr * 8)) != PVX_OK) return rc;
     return nfr;
 }
 
@@ -2129,14 +2020,11 @@ extern "C" int64_t pvx_funcwind_dev(const double* d_x, int x_complex, int64_t n,
     const int64_t nfr = pvx_nframes(n, wlen, hop);
     if (nfr == 0) return 0;
     if (!d_x || !d_out) { pvx_set_error("null funcwind array"); return PVX_ERR_INVALID; }
-    DevBuf dw;
-    if ((rc = dw.alloc((size_t)wlen * 8)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipMemcpy(dw.p, wind, (size_t)wlen * 8, hipMemcpyHostToDevice));
     ReduceParams rp = {};
-    rp.x = d_x; rp.wind = (const double*)dw.p; rp.nfr = nfr; rp.wlen = wlen; rp.hop = hop; rp.norm = divisor; rp.out = d_out;
-    if ((rc = pvx_launch_funcwind(rp, func, x_complex != 0, (hipStream_t)stream)) != PVX_OK) return rc;
-    PVX_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));            // dw is a local
-    return nfr;
+    rp.x = d_x; rp.nfr = nfr; rp.wlen = wlen; rp.hop = hop; rp.norm = divisor; rp.out = d_out;
+    rc = reduce_with_window(rp, wind, (hipStream_t)stream,
+                            [&](const ReduceParams& q, hipStream_t s) { return pvx_launch_funcwind(q, func, x_complex != 0, s); });
+    return rc == PVX_OK ? nfr : rc;
 }
 
 extern "C" int64_t pvx_funcwind(const double* x, int x_complex, int64_t n, const double* wind, int wlen, int hop, int func, double divisor, double* out) {
@@ -2148,12 +2036,12 @@ extern "C" int64_t pvx_funcwind(const double* x, int x_complex, int64_t n, const
     if (!x || !out) { pvx_set_error("null funcwind array"); return PVX_ERR_INVALID; }
     const size_t xb = (size_t)n * (x_complex ? 16 : 8);
     const size_t ob = (size_t)nfr * ((x_complex && (func == PVX_FW_SUM || func == PVX_FW_MEAN)) ? 16 : 8);
-    DevBuf dx, dout;
+    DevMem dx, dout;
     if ((rc = dx.alloc(xb)) != PVX_OK || (rc = dout.alloc(ob)) != PVX_OK) return rc;
-    if ((rc = host_to_device(dx.p, x, xb)) != PVX_OK) return rc;
-    const int64_t r = pvx_funcwind_dev((const double*)dx.p, x_complex, n, wind, wlen, hop, func, divisor, (double*)dout.p, nullptr);
+    if ((rc = host_to_device(dx.get(), x, xb)) != PVX_OK) return rc;
+    const int64_t r = pvx_funcwind_dev(dx.as<const double>(), x_complex, n, wind, wlen, hop, func, divisor, dout.as<double>(), nullptr);
     if (r < 0) return r;
-    if ((rc = device_to_host(out, dout.p, ob)) != PVX_OK) return rc;
+    if ((rc = device_to_host(out, dout.get(), ob)) != PVX_OK) return rc;
     return nfr;
 }
 
@@ -2224,15 +2112,15 @@ extern "C" int64_t pvx_periodicity(const double* x, int64_t nsamp, const double*
     if (nidx == 0) return 0;
     if (!x || !cand_period || !cand_strength || !ncands || !preferred) { pvx_set_error("null periodicity array"); return PVX_ERR_INVALID; }
     const size_t cb = (size_t)nidx * ncand * 8, ib = (size_t)nidx * 4;
-    DevBuf dx, dp, ds, dn, dq;
+    DevMem dx, dp, ds, dn, dq;
     if ((rc = dx.alloc((size_t)nsamp * 8)) != PVX_OK || (rc = dp.alloc(cb)) != PVX_OK || (rc = ds.alloc(cb)) != PVX_OK ||
         (rc = dn.alloc(ib)) != PVX_OK || (rc = dq.alloc(ib)) != PVX_OK) return rc;
-    if ((rc = host_to_device(dx.p, x, (size_t)nsamp * 8)) != PVX_OK) return rc;
-    const int64_t r = pvx_periodicity_dev((const double*)dx.p, nsamp, wind, nwind, idx, nidx, method, cand_method, mindelay, maxdelay, threshold,
-                                          vthresh, ncand, fftthresh, (double*)dp.p, (double*)ds.p, (int32_t*)dn.p, (int32_t*)dq.p, nullptr);
+    if ((rc = host_to_device(dx.get(), x, (size_t)nsamp * 8)) != PVX_OK) return rc;
+    const int64_t r = pvx_periodicity_dev(dx.as<const double>(), nsamp, wind, nwind, idx, nidx, method, cand_method, mindelay, maxdelay, threshold,
+                                          vthresh, ncand, fftthresh, dp.as<double>(), ds.as<double>(), dn.as<int32_t>(), dq.as<int32_t>(), nullptr);
     if (r < 0) return r;
-    if ((rc = device_to_host(cand_period, dp.p, cb)) != PVX_OK || (rc = device_to_host(cand_strength, ds.p, cb)) != PVX_OK ||
-        (rc = device_to_host(ncands, dn.p, ib)) != PVX_OK || (rc = device_to_host(preferred, dq.p, ib)) != PVX_OK) return rc;
+    if ((rc = device_to_host(cand_period, dp.get(), cb)) != PVX_OK || (rc = device_to_host(cand_strength, ds.get(), cb)) != PVX_OK ||
+        (rc = device_to_host(ncands, dn.get(), ib)) != PVX_OK || (rc = device_to_host(preferred, dq.get(), ib)) != PVX_OK) return rc;
     return nidx;
 }
 
@@ -2284,16 +2172,16 @@ extern "C" int64_t pvx_filterbank(const void* x, int x_dtype, int64_t n, const d
     int64_t fc = (int64_t)(limit / es) > nwind ? ((int64_t)(limit / es) - nwind) / hop + 1 : 1;
     fc = std::min<int64_t>(fc, std::max<int64_t>(1, (int64_t)(limit / std::max(sb, cb))));
     fc = std::min(fc, nfr);
-    DevBuf dx, ds, dc;
+    DevMem dx, ds, dc;
     if ((rc = dx.alloc((size_t)((fc - 1) * hop + nwind) * es)) != PVX_OK || (spec && (rc = ds.alloc((size_t)fc * sb)) != PVX_OK) ||
         (cep && (rc = dc.alloc((size_t)fc * cb)) != PVX_OK)) return rc;
     for (int64_t f0 = 0; f0 < nfr; f0 += fc) {
         const int64_t cnt = std::min(fc, nfr - f0);
-        if ((rc = host_to_device(dx.p, (const char*)x + (size_t)(f0 * hop) * es, (size_t)((cnt - 1) * hop + nwind) * es)) != PVX_OK) return rc;
-        if ((rc = pvx_fbank_run(dx.p, x_dtype, cnt, wind, nwind, hop, fb, nband, cep_mode, spec ? (double*)ds.p : nullptr,
-                                cep ? (double*)dc.p : nullptr, nullptr, &t_fbank_kernels)) != PVX_OK) return rc;
-        if (spec && (rc = device_to_host((char*)spec + (size_t)f0 * sb, ds.p, (size_t)cnt * sb)) != PVX_OK) return rc;
-        if (cep && (rc = device_to_host((char*)cep + (size_t)f0 * cb, dc.p, (size_t)cnt * cb)) != PVX_OK) return rc;
+        if ((rc = host_to_device(dx.get(), (const char*)x + (size_t)(f0 * hop) * es, (size_t)((cnt - 1) * hop + nwind) * es)) != PVX_OK) return rc;
+        if ((rc = pvx_fbank_run(dx.get(), x_dtype, cnt, wind, nwind, hop, fb, nband, cep_mode, spec ? ds.as<double>() : nullptr,
+                                cep ? dc.as<double>() : nullptr, nullptr, &t_fbank_kernels)) != PVX_OK) return rc;
+        if (spec && (rc = device_to_host((char*)spec + (size_t)f0 * sb, ds.get(), (size_t)cnt * sb)) != PVX_OK) return rc;
+        if (cep && (rc = device_to_host((char*)cep + (size_t)f0 * cb, dc.get(), (size_t)cnt * cb)) != PVX_OK) return rc;
     }
     return nfr;
 }
@@ -2330,7 +2218,7 @@ extern "C" int pvx_pack_rows_dev(const pvx_plan* plan, int64_t rows, const doubl
     if (!d_f || !d_mag || !d_ph || !d_binno || !d_totalmag || !d_wire) { pvx_set_error("null wire array"); return PVX_ERR_INVALID; }
     WireParams wp = {};
     wp.rows = rows; wp.K = plan->npks; wp.precision = plan->precision; wp.fstep = plan->fstep; wp.wire = d_wire;
-    wp.fmt = plan->wire_fmt; wp.dt = plan->dt; wp.wfbin = plan->d_wfbin;
+    wp.fmt = plan->wire_fmt; wp.dt = plan->dt; wp.wfbin = plan->d_wfbin.as<double>();
     wp.f = d_f; wp.mag = d_mag; wp.ph = d_ph; wp.binno = d_binno; wp.totalmag = d_totalmag;
     return pvx_launch_wire(wp, true, (hipStream_t)stream);
 }
@@ -2364,8 +2252,8 @@ extern "C" int64_t pvx_analyze_dev_wire(pvx_plan* p, const void* d_x, int x_dtyp
         return rc == PVX_OK ? F : rc;
     }
     const size_t per_frame_out = (size_t)(5 * p->npks + 2) * sizeof(double);
-    if ((rc = grow_dev(&p->d_wiretmp, &p->wiretmp_cap, (size_t)rows * per_frame_out)) != PVX_OK) return rc;
-    const HostOut o = block_ptrs(p->d_wiretmp, rows, p->npks);
+    if ((rc = p->d_wiretmp.grow((size_t)rows * per_frame_out, Sizing::headroom)) != PVX_OK) return rc;
+    const HostOut o = block_ptrs(p->d_wiretmp.as<double>(), rows, p->npks);
     rc = analyze_rows(p, route, d_x, x_dtype, nsamp, nsig, sig_stride, F, o.f, o.mag, o.ph, o.realph, o.binno, nullptr, o.totalmag, nullptr, (hipStream_t)stream);
     if (rc != PVX_OK) return rc;
     rc = pvx_pack_rows_dev(p, rows, o.f, o.mag, o.ph, o.binno, o.totalmag, d_wire, stream);
@@ -2381,7 +2269,7 @@ extern "C" int pvx_unpack_rows_dev(const pvx_plan* plan, int64_t rows, const voi
     if (!d_f || !d_mag || !d_ph || !d_realph || !d_binno || !d_totalmag || !d_wire) { pvx_set_error("null wire array"); return PVX_ERR_INVALID; }
     WireParams wp = {};
     wp.rows = rows; wp.K = plan->npks; wp.precision = plan->precision; wp.fstep = plan->fstep; wp.wire = (void*)d_wire;
-    wp.fmt = plan->wire_fmt; wp.dt = plan->dt; wp.wfbin = plan->d_wfbin;
+    wp.fmt = plan->wire_fmt; wp.dt = plan->dt; wp.wfbin = plan->d_wfbin.as<double>();
     wp.of = d_f; wp.omag = d_mag; wp.oph = d_ph; wp.orealph = d_realph; wp.obinno = d_binno; wp.ototalmag = d_totalmag;
     return pvx_launch_wire(wp, false, (hipStream_t)stream);
 }
@@ -2458,20 +2346,20 @@ extern "C" int pvx_synth_flags(const double* f, const double* mag, const double*
     const int64_t need = pvx_synth_len(maxend, nfft, hop_analysis, hop_synth, edge);
     if (need < 0 || need != wlen) { pvx_set_error("output length %lld, expected %lld", (long long)wlen, (long long)need); return PVX_ERR_SIZE; }
     const size_t n = (size_t)F * K;
-    DevBuf df, dm, dr, dpid, dst, dln, dw;
+    DevMem df, dm, dr, dpid, dst, dln, dw;
     if ((rc = df.alloc(n * 8)) != PVX_OK || (rc = dm.alloc(n * 8)) != PVX_OK || (rc = dr.alloc(n * 8)) != PVX_OK ||
         (rc = dpid.alloc(n * 4)) != PVX_OK || (rc = dst.alloc((size_t)P * 4)) != PVX_OK ||
         (rc = dln.alloc((size_t)P * 4)) != PVX_OK || (rc = dw.alloc((size_t)wlen * 8)) != PVX_OK)
         return rc;
-    if ((rc = host_to_device(df.p, f, n * 8)) != PVX_OK || (rc = host_to_device(dm.p, mag, n * 8)) != PVX_OK || (rc = host_to_device(dr.p, realph, n * 8)) != PVX_OK ||
-        (rc = host_to_device(dpid.p, partial_id, n * 4)) != PVX_OK || (rc = host_to_device(dst.p, part_start, (size_t)P * 4)) != PVX_OK ||
-        (rc = host_to_device(dln.p, part_len, (size_t)P * 4)) != PVX_OK) return rc;
-    rc = pvx_synth_dev_flags((const double*)df.p, (const double*)dm.p, (const double*)dr.p, (const int32_t*)dpid.p, F, K,
-                             (const int32_t*)dst.p, (const int32_t*)dln.p, P, sr, nfft, hop_analysis, hop_synth, edge, minframes,
-                             (double*)dw.p, wlen, nullptr, flags);
+    if ((rc = host_to_device(df.get(), f, n * 8)) != PVX_OK || (rc = host_to_device(dm.get(), mag, n * 8)) != PVX_OK || (rc = host_to_device(dr.get(), realph, n * 8)) != PVX_OK ||
+        (rc = host_to_device(dpid.get(), partial_id, n * 4)) != PVX_OK || (rc = host_to_device(dst.get(), part_start, (size_t)P * 4)) != PVX_OK ||
+        (rc = host_to_device(dln.get(), part_len, (size_t)P * 4)) != PVX_OK) return rc;
+    rc = pvx_synth_dev_flags(df.as<const double>(), dm.as<const double>(), dr.as<const double>(), dpid.as<const int32_t>(), F, K,
+                             dst.as<const int32_t>(), dln.as<const int32_t>(), P, sr, nfft, hop_analysis, hop_synth, edge, minframes,
+                             dw.as<double>(), wlen, nullptr, flags);
     if (rc != PVX_OK) return rc;
     PVX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    if ((rc = device_to_host(w, dw.p, (size_t)wlen * 8)) != PVX_OK) return rc;
+    if ((rc = device_to_host(w, dw.get(), (size_t)wlen * 8)) != PVX_OK) return rc;
     return PVX_OK;
 }
 
