@@ -524,7 +524,7 @@ class PV(object):
                     ratio = fa[:, None, :] / fa[:, :, None]           # [frame, j, c] = f_c / f_j
                     hn = np.round(ratio)
                     hn[hn == 0] = 1
-                    inh = np.abs(ratio / hn - 1)                      # |f_c / n / f_j - 1|
+                    inh = np.abs(fa[:, None, :] / hn / fa[:, :, None] - 1)   # |f_c / n / f_j - 1|, divided in that order (:284)
                     comp = (inh < f_threshold) & va[:, None, :] & va[:, :, None]
                     nharm[a:a + step] = comp.sum(axis=2)
                     hpower[a:a + step] = (comp * rowpow[None, None, :]).sum(axis=2)

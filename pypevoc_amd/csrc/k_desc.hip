@@ -18,7 +18,11 @@ __global__ __launch_bounds__(256) void k_f0(const double* __restrict__ f, const 
     if (fr >= F) return;
     const double* ff = f + fr * K;
     const double* mm = mag + fr * K;
-    double maxmag = mm[0];                                            // np.max (PVAnalysis.py:381)
+    // Maximum of the magnitudes that are not NaN (np.nanmax): a NaN is replaced by the next value and never taken in.
+    // The reference's np.max (PVAnalysis.py:381) would propagate it, but a resident row never holds a NaN beside finite
+    // entries -- a frame with a NaN sample has no peaks at all -- so on the arrays this kernel sees the two agree
+    // (tests/test_consumers_gpu.py::test_f0_of_a_signal_with_a_nan_sample).
+    double maxmag = mm[0];
     for (int k = 1; k < K; k++) maxmag = (mm[k] > maxmag || maxmag != maxmag) ? mm[k] : maxmag;
     const double lim = maxmag * thr;
     double best = 0.0;
