@@ -36,6 +36,11 @@ constexpr int GFR = 8;              // frames staged before the per-peak pass
 #ifndef PVX_PRIO_C
 #define PVX_PRIO_C 0
 #endif
+// the candidates' phase at nfft 2048 (see the frame loop; -DPVX_CAND_INTERIOR=0 for A/B builds): the neighbour reads of a frame
+// whose candidates all sit well inside a quarter of the buffer, at fixed offsets from one address
+#ifndef PVX_CAND_INTERIOR
+#define PVX_CAND_INTERIOR 1
+#endif
 
 typedef unsigned short u16;
 // a kept peak's results: non-temporal stores (written once, read by nobody in the launch: +1.3 % at nfft 2048 / npks 8 for leaving the caches
@@ -684,30 +689,58 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
                 // ranking, the selected-bin list, the salience test and the staging.  Same selection as
                 // peak_pick_regs: rank by (score desc, bin asc), the npeaks best; then the salience filter.
                 const bool has = lane < C;
-                const int pb = has ? (int)Lci[lane] : 1;
+                // (a lane without a candidate keeps nothing, whatever it reads.  nfft 2048: it reads around bin 8, not bin 1 -- bin 1 would
+                // fail the interior ballot below on every frame with fewer than 64 candidates)
+                const int pb = has ? (int)Lci[lane] : (X4 ? 8 : 1);
                 const int rad = p.rad;
                 const int lo = pb - rad > 1 ? pb - rad : 1;
                 int hi = pb + rad < M ? pb + rad : M;
                 hi = hi > M - 1 ? M - 1 : hi;
-                const float2 c = cur[XA(pb)];
-                const float2 vm = cur[XA(pb - 1)], vp = cur[XA(pb + 1)];
+                float2 c, vm, vp;
                 float v;
                 float nb[10];
                 if constexpr (X4) {
-                    float2 nx[10];
+                    // ---- interior frames (every frame of music): no candidate within 5 bins of bin 0, of bin M - 1 or of the end of
+                    // a 256-bin quarter of the buffer (bins 6 .. 249 of a quarter) and rad = 5.  Then no index below is clamped and
+                    // bins pb - 5 .. pb + 5 are eleven consecutive slots: ONE address per lane and immediate offsets, the centre and
+                    // its two neighbours being three of the eleven -- instead of thirteen clamped indices, each through xa4().  One
+                    // ballot decides for the wave; any other frame takes the clamped reads as before.  Same values either way.
+                    // (each branch's reads end in one empty asm that takes them all, PVX_PIN13: without it the compiler moves the reads
+                    // behind the branches' join as 4-byte reads of merged addresses, a wait between every two, and the fast path costs
+                    // more than it saves.  BOTH statements stay when either branch is edited; profiles/candidates_ab.txt has the
+                    // instruction counts to check a new listing against)
+                    v2f xv[13];                                      // c | vm | vp | the ten neighbours
+#define PVX_PIN13(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]), \
+                                      "+v"(a[9]), "+v"(a[10]), "+v"(a[11]), "+v"(a[12]))
+                    const v2f* const xs = (const v2f*)cur;
+                    bool interior = false;
+                    if constexpr (PVX_CAND_INTERIOR != 0) interior = rad == 5 && __ballot((unsigned)((pb & 255) - 6) > 243u) == 0ull;
+                    if (interior) {
+                        const v2f* const xc = xs + xa4(pb);
+                        xv[0] = xc[0]; xv[1] = xc[-1]; xv[2] = xc[1];
 #pragma unroll
-                    for (int d = 1; d <= 5; d++) {
-                        const int dd = d > rad ? rad : d;
-                        int j0 = pb - dd, j1 = pb + dd;
-                        j0 = j0 < lo ? lo : j0;
-                        j1 = j1 > hi ? hi : j1;
-                        nx[2 * d - 2] = cur[xa4(j0)];
-                        nx[2 * d - 1] = cur[xa4(j1)];
+                        for (int d = 1; d <= 5; d++) { xv[2 * d + 1] = xc[-d]; xv[2 * d + 2] = xc[d]; }
+                        PVX_PIN13(xv);
+                    } else {
+                        xv[0] = xs[xa4(pb)]; xv[1] = xs[xa4(pb - 1)]; xv[2] = xs[xa4(pb + 1)];
+#pragma unroll
+                        for (int d = 1; d <= 5; d++) {
+                            const int dd = d > rad ? rad : d;
+                            int j0 = pb - dd, j1 = pb + dd;
+                            j0 = j0 < lo ? lo : j0;
+                            j1 = j1 > hi ? hi : j1;
+                            xv[2 * d + 1] = xs[xa4(j0)];
+                            xv[2 * d + 2] = xs[xa4(j1)];
+                        }
+                        PVX_PIN13(xv);
                     }
+#undef PVX_PIN13
+                    c = make_float2(xv[0].x, xv[0].y); vm = make_float2(xv[1].x, xv[1].y); vp = make_float2(xv[2].x, xv[2].y);
                     v = norm2(c);
 #pragma unroll
-                    for (int d = 0; d < 10; d++) nb[d] = norm2(nx[d]);
+                    for (int d = 0; d < 10; d++) nb[d] = norm2(make_float2(xv[3 + d].x, xv[3 + d].y));
                 } else {
+                    c = cur[XA(pb)]; vm = cur[XA(pb - 1)]; vp = cur[XA(pb + 1)];
                     v = Ly[ymap<1>(pb)];
 #pragma unroll
                     for (int d = 1; d <= 5; d++) {
