@@ -377,6 +377,36 @@ int64_t pvx_funcwind(const double* x, int x_complex, int64_t n, const double* wi
 int64_t pvx_funcwind_dev(const double* d_x, int x_complex, int64_t n, const double* wind, int wlen, int hop,
                          int func, double divisor, double* d_out, void* stream);
 
+/* ---- HeterodyneHarmonic: every harmonic of one f0 track (pypevoc/Heterodyne.py:261-542) -----
+ *
+ * fvec: the track in cycles per sample (f0 / sr), one value per sample of x.  The heterodyning signal of harmonic h is
+ * exp(+2j*pi*h*cumsum(fvec)) (heterodyner_signal, :384-400); it is never materialised: the kernels keep the running sum
+ * in cycles and evaluate its harmonics on the spot.  float64, the framing of pvx_heterodyne.
+ *
+ * pvx_hetharm: extract_partial / extract_partials / calc_adjusted_freq's heterodyne (:460-471, :521-532, :425):
+ *   ah[i][k] = 2 * sum_j x[i*hop+j] * exp(+2j*pi*(first+k)*c[i*hop+j]) * wind[j] / sum(wind),  c = cumsum(fvec),
+ *   complex [nfr][count][2]; halve_dc != 0 halves the column of harmonic 0 (:530).  icent[i] = i*hop + wlen/2 (optional).
+ *   A column does not depend on which other harmonics the call asks for (bit for bit).  Returns nfr.
+ * pvx_hetharm_resynth: resynth_partial / resynth / filter_harmonic (:473-499, :534-538) from ah [nfr][nharm_total][2]
+ *   (nfr must be pvx_nframes(n, wlen, hop)):
+ *   y[t] = sum_{h=first}^{first+count-1} Re(conj(exp(2j*pi*h*c[t])) * hf_h[t]),  hf_h = np.interp(t/sr, th, ah[:, h]),
+ *   th[i] = (wlen/2 + i*hop)/sr, clamped to the end values.  filter != 0 zeroes hf_h[t] where f0 < fmin, f0 > fmax,
+ *   f0*h > sr/2.2 or |hf_h[t]| < ampthr * max|hf_h| (f0 = fvec*sr).  hf (optional, count == 1): hf_first itself, [n][2].
+ *   Returns n, or 0 without touching y when nfr == 0.
+ * `wind` is a HOST array in both variants; every other array of the `_dev` forms is device memory, the work runs on
+ * `stream` and is synchronised before the return.  Negative status on failure.
+ */
+int64_t pvx_hetharm(const double* x, int64_t n, const double* fvec, const double* wind, int wlen, int hop,
+                    int first, int count, int halve_dc, double* ah, int64_t* icent);
+int64_t pvx_hetharm_dev(const double* d_x, int64_t n, const double* d_fvec, const double* wind, int wlen, int hop,
+                        int first, int count, int halve_dc, double* d_ah, int64_t* d_icent, void* stream);
+int64_t pvx_hetharm_resynth(const double* fvec, int64_t n, const double* ah, int64_t nfr, int nharm_total, int wlen,
+                            int hop, int first, int count, int filter, double sr, double fmin, double fmax,
+                            double ampthr, double* y, double* hf);
+int64_t pvx_hetharm_resynth_dev(const double* d_fvec, int64_t n, const double* d_ah, int64_t nfr, int nharm_total,
+                                int wlen, int hop, int first, int count, int filter, double sr, double fmin,
+                                double fmax, double ampthr, double* d_y, double* d_hf, void* stream);
+
 /* ---- time-domain periodicity: PeriodSeries (pypevoc/Periodicity.py:251-503) ----------------
  *
  * pvx_periodicity: Periodicity._calc + sort_strength (Periodicity.py:98-236) for the frames centred at

@@ -97,6 +97,14 @@ SIGNATURES = {
                                         c_double_p, c_int64_p]),
     "pvx_heterodyne_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvx_hetharm": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, c_double_p, c_int64_p]),
+    "pvx_hetharm_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvx_hetharm_resynth": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int64] + [ctypes.c_int] * 6 +
+                            [ctypes.c_double] * 4 + [c_double_p, c_double_p]),
+    "pvx_hetharm_resynth_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int] * 6 +
+                                [ctypes.c_double] * 4 + [ctypes.c_void_p] * 3),
     "pvx_rms_frames": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p]),
     "pvx_funcwind": (ctypes.c_int64, [c_double_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_double, c_double_p]),

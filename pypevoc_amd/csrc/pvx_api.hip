@@ -2045,6 +2045,124 @@ extern "C" int64_t pvx_funcwind(const double* x, int x_complex, int64_t n, const
     return nfr;
 }
 
+// ---- harmonic heterodyne on one f0 track (k_hetharm.hip, Heterodyne.py:261-542) -----------------
+static int hetharm_args(int64_t n, const double* wind, int wlen, int hop, int first, int count, double* norm) {
+    int rc;
+    if ((rc = reduce_args(n, wind, wlen, hop, norm, 1)) != PVX_OK) return rc;
+    if (first < 0 || count < 1 || (int64_t)first + count > PVX_HH_MAX_HARM) {
+        pvx_set_error("pvx_hetharm: harmonics %d .. %lld (first >= 0, count >= 1, up to %d)", first, (long long)first + count - 1, PVX_HH_MAX_HARM);
+        return PVX_ERR_INVALID;
+    }
+    return PVX_OK;
+}
+
+// the running phase of d_fvec in a workspace of this call: cyc [n] and the scan's tile sums behind it
+static int hetharm_phase(const double* d_fvec, int64_t n, DevMem& ws, hipStream_t s) {
+    int rc;
+    if ((rc = ws.alloc(((size_t)n + (size_t)pvx_hh_tiles(n)) * 8)) != PVX_OK) return rc;
+    return pvx_launch_hh_phase(d_fvec, n, ws.as<double>(), ws.as<double>() + n, s);
+}
+
+extern "C" int64_t pvx_hetharm_dev(const double* d_x, int64_t n, const double* d_fvec, const double* wind, int wlen, int hop, int first,
+                                   int count, int halve_dc, double* d_ah, int64_t* d_icent, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    double norm;
+    if ((rc = hetharm_args(n, wind, wlen, hop, first, count, &norm)) != PVX_OK) return rc;
+    const int64_t nfr = pvx_nframes(n, wlen, hop);
+    if (nfr == 0) return 0;
+    if (!d_x || !d_fvec || !d_ah) { pvx_set_error("null hetharm array"); return PVX_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    DevMem dw, ws;
+    if ((rc = dw.alloc((size_t)wlen * 8)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemcpy(dw.get(), wind, (size_t)wlen * 8, hipMemcpyHostToDevice));
+    if ((rc = hetharm_phase(d_fvec, n, ws, s)) != PVX_OK) return rc;
+    HhExtractParams ep = {};
+    ep.x = d_x; ep.cyc = ws.as<const double>(); ep.wind = dw.as<const double>(); ep.nfr = nfr; ep.wlen = wlen; ep.hop = hop;
+    ep.first = first; ep.count = count; ep.halve_dc = halve_dc ? 1 : 0; ep.norm = norm; ep.ah = d_ah; ep.icent = d_icent;
+    rc = pvx_launch_hh_extract(ep, s);
+    PVX_HIP_CHECK(hipStreamSynchronize(s));                           // the workspaces go with this call
+    return rc == PVX_OK ? nfr : rc;
+}
+
+extern "C" int64_t pvx_hetharm(const double* x, int64_t n, const double* fvec, const double* wind, int wlen, int hop, int first, int count,
+                               int halve_dc, double* ah, int64_t* icent) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    double norm;
+    if ((rc = hetharm_args(n, wind, wlen, hop, first, count, &norm)) != PVX_OK) return rc;
+    const int64_t nfr = pvx_nframes(n, wlen, hop);
+    if (nfr == 0) return 0;
+    if (!x || !fvec || !ah) { pvx_set_error("null hetharm array"); return PVX_ERR_INVALID; }
+    const size_t ab = (size_t)nfr * count * 16;
+    DevMem dx, df, da, dic;
+    if ((rc = dx.alloc((size_t)n * 8)) != PVX_OK || (rc = df.alloc((size_t)n * 8)) != PVX_OK || (rc = da.alloc(ab)) != PVX_OK ||
+        (rc = dic.alloc((size_t)nfr * 8)) != PVX_OK) return rc;
+    if ((rc = host_to_device(dx.get(), x, (size_t)n * 8)) != PVX_OK || (rc = host_to_device(df.get(), fvec, (size_t)n * 8)) != PVX_OK) return rc;
+    const int64_t r = pvx_hetharm_dev(dx.as<const double>(), n, df.as<const double>(), wind, wlen, hop, first, count, halve_dc, da.as<double>(),
+                                      dic.as<int64_t>(), nullptr);
+    if (r < 0) return r;
+    if ((rc = device_to_host(ah, da.get(), ab)) != PVX_OK) return rc;
+    if (icent && (rc = device_to_host(icent, dic.get(), (size_t)nfr * 8)) != PVX_OK) return rc;
+    return nfr;
+}
+
+static int hetharm_resynth_args(int64_t n, int64_t nfr, int nharm_total, int wlen, int hop, int first, int count, int want_hf) {
+    if (n < 0 || wlen <= 0 || hop <= 0 || nharm_total < 1) { pvx_set_error("bad harmonic-resynthesis argument"); return PVX_ERR_INVALID; }
+    if (first < 0 || count < 1 || (int64_t)first + count > nharm_total || nharm_total > PVX_HH_MAX_HARM) {
+        pvx_set_error("pvx_hetharm_resynth: harmonics %d .. %lld of %d", first, (long long)first + count - 1, nharm_total);
+        return PVX_ERR_INVALID;
+    }
+    if (nfr != pvx_nframes(n, wlen, hop)) {
+        pvx_set_error("pvx_hetharm_resynth: %lld frames, %lld samples at window %d / hop %d have %lld", (long long)nfr, (long long)n, wlen, hop,
+                      (long long)pvx_nframes(n, wlen, hop));
+        return PVX_ERR_SIZE;
+    }
+    if (want_hf && count != 1) { pvx_set_error("pvx_hetharm_resynth: the interpolated amplitude is one harmonic's (count %d)", count); return PVX_ERR_INVALID; }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_hetharm_resynth_dev(const double* d_fvec, int64_t n, const double* d_ah, int64_t nfr, int nharm_total, int wlen, int hop,
+                                           int first, int count, int filter, double sr, double fmin, double fmax, double ampthr, double* d_y,
+                                           double* d_hf, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = hetharm_resynth_args(n, nfr, nharm_total, wlen, hop, first, count, d_hf != nullptr)) != PVX_OK) return rc;
+    if (nfr == 0) return 0;
+    if (!d_fvec || !d_ah || !d_y) { pvx_set_error("null harmonic-resynthesis array"); return PVX_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    DevMem ws, dmax;
+    if ((rc = hetharm_phase(d_fvec, n, ws, s)) != PVX_OK) return rc;
+    if (filter && (rc = dmax.alloc((size_t)count * 8)) != PVX_OK) return rc;
+    HhResynthParams rp = {};
+    rp.fvec = d_fvec; rp.cyc = ws.as<const double>(); rp.ah = d_ah; rp.n = n; rp.nfr = nfr; rp.nharm_total = nharm_total; rp.wlen = wlen;
+    rp.hop = hop; rp.first = first; rp.count = count; rp.filter = filter ? 1 : 0; rp.sr = sr; rp.fmin = fmin; rp.fmax = fmax; rp.ampthr = ampthr;
+    rp.amax = dmax.as<double>(); rp.y = d_y; rp.hf = d_hf;
+    rc = pvx_launch_hh_resynth(rp, s);
+    PVX_HIP_CHECK(hipStreamSynchronize(s));
+    return rc == PVX_OK ? n : rc;
+}
+
+extern "C" int64_t pvx_hetharm_resynth(const double* fvec, int64_t n, const double* ah, int64_t nfr, int nharm_total, int wlen, int hop, int first,
+                                       int count, int filter, double sr, double fmin, double fmax, double ampthr, double* y, double* hf) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = hetharm_resynth_args(n, nfr, nharm_total, wlen, hop, first, count, hf != nullptr)) != PVX_OK) return rc;
+    if (nfr == 0) return 0;
+    if (!fvec || !ah || !y) { pvx_set_error("null harmonic-resynthesis array"); return PVX_ERR_INVALID; }
+    const size_t ab = (size_t)nfr * nharm_total * 16;
+    DevMem df, da, dy, dh;
+    if ((rc = df.alloc((size_t)n * 8)) != PVX_OK || (rc = da.alloc(ab)) != PVX_OK || (rc = dy.alloc((size_t)n * 8)) != PVX_OK ||
+        (hf && (rc = dh.alloc((size_t)n * 16)) != PVX_OK)) return rc;
+    if ((rc = host_to_device(df.get(), fvec, (size_t)n * 8)) != PVX_OK || (rc = host_to_device(da.get(), ah, ab)) != PVX_OK) return rc;
+    const int64_t r = pvx_hetharm_resynth_dev(df.as<const double>(), n, da.as<const double>(), nfr, nharm_total, wlen, hop, first, count, filter, sr,
+                                              fmin, fmax, ampthr, dy.as<double>(), hf ? dh.as<double>() : nullptr, nullptr);
+    if (r < 0) return r;
+    if ((rc = device_to_host(y, dy.get(), (size_t)n * 8)) != PVX_OK) return rc;
+    if (hf && (rc = device_to_host(hf, dh.get(), (size_t)n * 16)) != PVX_OK) return rc;
+    return n;
+}
+
 // ---- time-domain periodicity (k_period.hip) ---------------------------------------------------
 // numpy's clipping of a slice bound on an array of `len` entries
 static int np_bound(int64_t b, int64_t len) {

@@ -268,6 +268,39 @@ int pvx_launch_reduce(const ReduceParams& p, int mode, hipStream_t s);
 // FuncWind's named reducers (func: pvx_funcwind_op); x complex128 when cpx (p.x then points at [n][2])
 int pvx_launch_funcwind(const ReduceParams& p, int func, bool cpx, hipStream_t s);
 
+// harmonic heterodyne on one f0 track (k_hetharm.hip, Heterodyne.py:261-542).  Every pointer is device memory.
+#define PVX_HH_TILE 2048          // samples per block of the phase scan
+#define PVX_HH_GROUP 8            // harmonics a wave of k_hh_extract walks by complex multiplication
+#define PVX_HH_MAX_HARM (1 << 20) // first + count: far beyond sr / 2 / f0 of any track, keeps the index arithmetic in int
+inline int64_t pvx_hh_tiles(int64_t n) { return (n + PVX_HH_TILE - 1) / PVX_HH_TILE; }
+// cyc[t] = fvec[0] + .. + fvec[t] (np.cumsum's indexing), in cycles; tsum: pvx_hh_tiles(n) doubles of workspace
+int pvx_launch_hh_phase(const double* fvec, int64_t n, double* cyc, double* tsum, hipStream_t s);
+struct HhExtractParams {
+    const double* x;          // [n]
+    const double* cyc;        // [n] running sum of fvec (pvx_launch_hh_phase)
+    const double* wind;       // [wlen]
+    int64_t nfr;
+    int wlen, hop;
+    int first, count;         // harmonics first .. first + count - 1
+    int halve_dc;             // column of harmonic 0 is halved (extract_partials, Heterodyne.py:530)
+    double norm;              // sum(wind)
+    double* ah;               // [nfr][count][2]
+    int64_t* icent;           // [nfr] optional
+};
+int pvx_launch_hh_extract(const HhExtractParams& p, hipStream_t s);
+struct HhResynthParams {
+    const double* fvec;       // [n] cycles per sample
+    const double* cyc;        // [n]
+    const double* ah;         // [nfr][nharm_total][2]
+    int64_t n, nfr;
+    int nharm_total, wlen, hop, first, count, filter;
+    double sr, fmin, fmax, ampthr;
+    double* amax;             // [count] workspace: max_i |ah[i][h]| (filter only)
+    double* y;                // [n]
+    double* hf;               // [n][2] optional, count == 1: the interpolated (and filtered) amplitude itself
+};
+int pvx_launch_hh_resynth(const HhResynthParams& p, hipStream_t s);
+
 // time-domain periodicity (k_period.hip, Periodicity.py:98-236).  Lag ranges lo[r]..hi[r] are the similarity lags a frame
 // reads; ns..ne the normaliser slice in the index space of the reference's array (amdf: lag; xcorr: nwind-1+lag).
 #define PVX_PERIOD_MAX_NCAND 64
