@@ -459,6 +459,36 @@ int64_t pvx_filterbank_dev(const void* d_x, int x_dtype, int64_t n, const double
                            const double* fb, int nband, int cep_mode, double* d_spec, double* d_cep, void* stream);
 const char* pvx_filterbank_last_kernels(void);
 
+/* ---- windowed spectral measures (pypevoc/SoundUtils.py: SpecCentWind :142-160, SpecFlux :196-231;
+ *      pypevoc/speech/SpeechAnalysis.py: SpectralMoments :82-139) ----
+ *
+ * Over the half spectrum |X_i[k]|, k = 0 .. nwind/2, of the frames X_i = fft(x[i*hop : i*hop+nwind] * wind):
+ *   PVX_SD_RATIO  out[i] = sum_k a[k] |X_i[k]| / sum_k b[k] |X_i[k]|                   out [nfr]
+ *   PVX_SD_FLUX   out[i] = sqrt(sum_k a[k] (|X_i[k]| - |X_{i+1}[k]|)^2)              out [nfr], reads frames 0 .. nfr
+ *   PVX_SD_PSD    out[k] = (1/nfr) sum_i |X_i[k]|^2, k < nwind/2                      out [nwind/2]; a, b unused
+ * a, b: host arrays of nwind/2 + 1 weights per half-spectrum bin (b: RATIO only): the caller folds the reference's bin
+ * ranges of the full spectrum onto them (bin k and bin nwind - k share a magnitude).  wind: host array [nwind], the bare
+ * window.  nfr is the caller's: the three reference functions count their frames differently (pvx_nframes(n, ..),
+ * pvx_nframes(n - hop, ..), int((n - nwind - 1) / hop)); the last frame read must lie inside n, else PVX_ERR_SIZE.
+ * nfr = 0: nothing is launched, out is untouched.
+ * x: float32, float64 or int16 samples (pvx_dtype), widened on load; all arithmetic float64, every sum in a fixed order:
+ * a value does not depend on the grid, on the other frames of the call or on where the samples came from.  The
+ * periodogram adds its frames in blocks of PVX_SPECDESC_BLOCK and the blocks' sums in index order.  nwind 512 / 1024 /
+ * 2048 run one fused kernel (PSD: and the pass over the block sums), any other nwind k_frames + rocFFT + one kernel per
+ * batch of rows; PVX_SPECDESC_ROWS in the environment sends every nwind down the rows route.  Host input is chunked by
+ * PVX_MAX_DEVICE_BYTES (PSD: in whole blocks, at least one).  pvx_specdesc_dev: x and out are device memory (wind, a, b
+ * stay host arrays), work on `stream`, synchronised before the return.  Both return nfr or a negative status; calls
+ * share the filter banks' per-device workspace and take turns on it.  pvx_specdesc_last_kernels: what the calling
+ * thread's last call ran ("k_specdesc_fused<1024>", "k_frames+rocfft+k_specdesc_rows"; "" when it had no frame).
+ */
+#define PVX_SPECDESC_BLOCK 16
+typedef enum { PVX_SD_RATIO = 0, PVX_SD_FLUX = 1, PVX_SD_PSD = 2 } pvx_specdesc_measure;
+int64_t pvx_specdesc(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int measure,
+                     const double* a, const double* b, double* out);
+int64_t pvx_specdesc_dev(const void* d_x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr,
+                         int measure, const double* a, const double* b, double* d_out, void* stream);
+const char* pvx_specdesc_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

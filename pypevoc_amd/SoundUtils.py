@@ -2,7 +2,12 @@
 framing: RMSWind (:71-103), Heterodyn (:106-117), HeterodynWithF0Track (:120-138).  The per-frame
 reductions run as HIP kernels (k_reduce.hip); building the heterodyning signal is host numpy as in the
 reference.  FuncWind (:42-69) runs on the device for the named reducers np.sum / np.mean / np.max / np.min / np.std /
-np.var (k_funcwind); an arbitrary Python callable has no device form and raises TypeError."""
+np.var (k_funcwind); an arbitrary Python callable has no device form and raises TypeError.
+SpecCentWind (:142-160) and SpecFlux (:196-231) run in k_specdesc.hip (pvx_specdesc, include/pvx.h; SPECDESC.md): the host
+folds the reference's bin ranges of the full spectrum onto weights per half-spectrum bin, everything per frame is on the
+device.  AvgWind (:163-193) is FuncWind's sum.  No CPU fallback."""
+import ctypes
+
 import numpy as np
 
 from . import _lib
@@ -105,3 +110,118 @@ def HeterodynWithF0Track(x, tf0, f0, sr=1, nwind=1024, nhop=512, windfunc=np.bla
     f0s = np.interp(tx, tf0[valid_idx], f0[valid_idx])
     phs = np.cumsum(2 * np.pi * f0s / sr)
     return _het(x, np.exp(1j * phs), sr, nwind, nhop, windfunc)
+
+
+# ---- windowed spectral measures (k_specdesc.hip) --------------------------------------------------------------------
+SD_RATIO, SD_FLUX, SD_PSD = 0, 1, 2                                   # pvx_specdesc_measure of include/pvx.h
+SD_BLOCK = 16                                                         # PVX_SPECDESC_BLOCK
+
+
+def fold_bins(bins, nwind):
+    """How many of the full-spectrum bins `bins` (indexes into range(nwind)) fall onto each half-spectrum bin 0 .. nwind//2:
+    bin k and bin nwind - k of a real frame's spectrum share a magnitude."""
+    bins = np.asarray(bins, dtype=np.int64)
+    c = np.zeros(int(nwind) // 2 + 1)
+    np.add.at(c, np.minimum(bins, int(nwind) - bins), 1.0)
+    return c
+
+
+def specdesc_run(x, wind, hop, nfr, measure, a=None, b=None):
+    """pvx_specdesc on x: nfr values (ratio, flux) or the mean power of nfr frames over bins 0 .. nwind//2 - 1 (psd), as a
+    host float64 array.  x: a host array, or a float32 / float64 / int16 1-D signal already on the GPU (a torch tensor,
+    anything with __cuda_array_interface__), read in place.  Raises PvxError without a GPU.  nfr <= 0: an empty array; the
+    library is told (last_kernels() is '' afterwards) and launches nothing."""
+    lib = _lib.load()
+    bound = _lib.init()
+    wind = np.ascontiguousarray(wind, dtype=np.float64)
+    nwind, hop, nfr = len(wind), int(hop), max(int(nfr), 0)
+    nout = nwind // 2 if measure == SD_PSD else nfr
+    tabs = [None if t is None else np.ascontiguousarray(t, dtype=np.float64) for t in (a, b)]
+    for t in tabs:
+        if t is not None and t.shape != (nwind // 2 + 1,):
+            raise ValueError("weights per half-spectrum bin must be [%d]: got %r" % (nwind // 2 + 1, t.shape))
+    pa, pb = [None if t is None else _lib.dptr(t) for t in tabs]
+    if _lib.is_device_array(x):
+        import torch
+        sig = _lib.DeviceSignal(x)
+        if len(sig.shape) != 1:
+            raise ValueError("a 1-D signal is expected")
+        if torch.cuda.current_device() != bound:                     # the output and the stream must be the bound device's
+            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
+                                % (torch.cuda.current_device(), bound))
+        dout = torch.empty(max(nout, 1), dtype=torch.float64, device=torch.device("cuda", bound))
+        stream = torch.cuda.current_stream()
+        got = _lib.check(lib.pvx_specdesc_dev(ctypes.c_void_p(sig.ptr), sig.dtype_code, sig.shape[0], _lib.dptr(wind), nwind, hop, nfr, measure,
+                                              pa, pb, ctypes.c_void_p(dout.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "pvx_specdesc_dev")
+        out = dout.cpu().numpy()[:nout]
+    else:
+        xs, code = _lib.as_signal(x)
+        if xs.ndim != 1:
+            raise ValueError("a 1-D signal is expected")
+        out = np.empty(nout)
+        got = _lib.check(lib.pvx_specdesc(ctypes.c_void_p(xs.ctypes.data), code, len(xs), _lib.dptr(wind), nwind, hop, nfr, measure, pa, pb,
+                                          _lib.dptr(out)), "pvx_specdesc")
+    assert got == nfr, (got, nfr)
+    return out if nfr else np.zeros(0)
+
+
+def _siglen(x):
+    return int(_lib.DeviceSignal(x).shape[0]) if _lib.is_device_array(x) else len(x)
+
+
+def last_kernels():
+    """The kernels the calling thread's last SpecCentWind / SpecFlux / SpectralMoments ran: 'k_specdesc_fused<1024>',
+    'k_frames+rocfft+k_specdesc_rows' ('' when it had no frame)."""
+    return _lib.load().pvx_specdesc_last_kernels().decode()
+
+
+def SpecCentWind(x, sr=1, nwind=1024, nhop=512, windfunc=np.blackman):
+    '''
+    Calculates the SpectralCentroid of x, in frames of
+    length nwind, and in steps of nhop.
+
+    The frames are windowed by np.blackman(nwind) whatever windfunc is: the reference does not hand windfunc on to
+    FuncWind (SoundUtils.py:157-158).  Bins 0 .. nwind//2 - 1, frequencies k/nwind*sr.
+    '''
+    nwind, nhop = int(nwind), int(nhop)
+    half = nwind // 2
+    a = np.zeros(half + 1)
+    b = np.zeros(half + 1)
+    a[:half] = np.arange(half) / float(nwind) * sr                    # :150
+    b[:half] = 1.0
+    nfr = _lib.nframes_host(_siglen(x), nwind, nhop)
+    ist = np.arange(nfr) * nhop
+    t = (ist + ist + nwind) / 2.0 / float(sr)                         # :66
+    return specdesc_run(x, np.blackman(nwind), nhop, nfr, SD_RATIO, a, b), t
+
+
+def flux_band(sr, nwind, minf=0, maxf=np.inf):
+    """The full-spectrum bins SpecFlux sums over (SoundUtils.py:211-216, 225): range(nwind)[minbin:maxbin]."""
+    minbin = int(minf / sr * nwind)
+    maxbinf = (float(maxf) / sr * nwind)
+    if maxbinf > nwind:
+        maxbin = nwind
+    else:
+        maxbin = int(maxbinf)
+    return np.arange(nwind)[minbin:maxbin]
+
+
+def SpecFlux(x, sr=1, nwind=1024, nhop=512, minf=0, maxf=np.inf, windfunc=np.blackman):
+    '''
+    Calculates the spectral flux between the frames at ist and ist + nhop: the norm of the difference of their magnitude
+    spectra over the bins from minf to maxf (bins of the full spectrum: a band above sr/2 counts the mirrored bins)
+    '''
+    nwind, nhop = int(nwind), int(nhop)
+    c = fold_bins(flux_band(sr, nwind, minf, maxf), nwind)
+    nfr = _lib.nframes_host(_siglen(x) - nhop, nwind, nhop)          # :218: while iend < nsam - nhop
+    ist = np.arange(nfr) * nhop
+    t = (ist + ist + nwind + nhop) / 2.0 / float(sr)                  # :226
+    return specdesc_run(x, windfunc(nwind), nhop, nfr, SD_FLUX, c), t
+
+
+def AvgWind(x, sr=1, nwind=1024, nhop=512, windfunc=np.blackman):
+    '''
+    Calculates the windowed average of x, in frames of
+    length nwind, and in steps of nhop: sum(xw)/sum(wind)
+    '''
+    return FuncWind(np.sum, x, sr=sr, nwind=nwind, nhop=nhop, power=1, windfunc=windfunc)

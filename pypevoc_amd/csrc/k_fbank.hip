@@ -21,6 +21,7 @@
 #include <mutex>
 #include <vector>
 
+#include "pvx_fbank_ws.h"
 #include "pvx_internal.h"
 #include "pvx_mem.h"
 #include "pvx_stft.h"
@@ -268,20 +269,7 @@ template <int R> int launch_fused(const FbankParams& p, int x_dtype, hipStream_t
     return PVX_OK;
 }
 
-// ---- per-device workspace: tables of the call, the rows route's buffers and rocFFT plans.  Kept for the process, grow-only,
-// held for a whole call (execution and the final synchronisation included): callers on one device take turns.
-struct FftPlan {
-    RealFft fft;
-    int64_t batch = 0;
-};
-struct FbankWs {
-    std::mutex mu;
-    std::vector<double> h_tab;                                        // host image of `tab` (alive until the call's copy is done)
-    std::vector<int> h_band;
-    DevMem tab, band, frames, spec;                                   // (exactly as large as the largest request so far)
-    DevMem work;                                                      // the one rocFFT work buffer the plans share
-    std::map<int, FftPlan> plans;                                     // nwind -> plan of the rows route
-};
+// ---- per-device workspace (pvx_fbank_ws.h): tables of the call, the rows route's buffers and rocFFT plans
 std::mutex g_ws_mu;
 std::map<int, FbankWs*> g_ws;                                         // device -> workspace (never erased)
 constexpr size_t kMaxPlans = 4;                                       // window lengths with a live rocFFT plan
@@ -294,7 +282,9 @@ int64_t rows_batch(int nwind) {
     return c < 1 ? 1 : c;
 }
 
-int ensure_plan(FbankWs& w, int nwind, FftPlan** out) {
+}  // namespace
+
+int pvx_fbank_ensure_plan(FbankWs& w, int nwind, FftPlan** out) {
     auto it = w.plans.find(nwind);
     if (it != w.plans.end()) { *out = &it->second; return PVX_OK; }
     if (w.plans.size() >= kMaxPlans) w.plans.clear();
@@ -323,6 +313,8 @@ int ensure_plan(FbankWs& w, int nwind, FftPlan** out) {
     *out = &(w.plans[nwind] = std::move(fp));
     return PVX_OK;
 }
+
+namespace {
 
 const double kPiD = 3.141592653589793238462643383279502884;
 
@@ -427,7 +419,7 @@ int run_locked(FbankWs& w, const void* d_x, int x_dtype, int64_t nfr, const doub
         if (rc != PVX_OK) return rc;
     } else {
         FftPlan* fp = nullptr;
-        if ((rc = ensure_plan(w, nwind, &fp)) != PVX_OK) return rc;
+        if ((rc = pvx_fbank_ensure_plan(w, nwind, &fp)) != PVX_OK) return rc;
         const int64_t batch = fp->batch;
         if ((rc = w.frames.grow((size_t)batch * nwind * 8, Sizing::exact)) != PVX_OK ||
             (rc = w.spec.grow((size_t)batch * nhalf * 16, Sizing::exact)) != PVX_OK) return rc;
@@ -453,18 +445,22 @@ int run_locked(FbankWs& w, const void* d_x, int x_dtype, int64_t nfr, const doub
 
 }  // namespace
 
+int pvx_fbank_workspace(FbankWs** ws) {
+    int dev = 0;
+    PVX_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    FbankWs*& e = g_ws[dev];
+    if (!e) e = new FbankWs();
+    *ws = e;
+    return PVX_OK;
+}
+
 int pvx_fbank_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_wind, int nwind, int hop, const double* h_fb, int nband,
                   int cep_mode, double* d_spec, double* d_cep, hipStream_t s, const char** kernels) {
     if (nfr <= 0) return PVX_OK;
-    int dev = 0;
-    PVX_HIP_CHECK(hipGetDevice(&dev));
     FbankWs* w;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        FbankWs*& e = g_ws[dev];
-        if (!e) e = new FbankWs();
-        w = e;
-    }
+    int rc;
+    if ((rc = pvx_fbank_workspace(&w)) != PVX_OK) return rc;
     std::lock_guard<std::mutex> lk(w->mu);
     return run_locked(*w, d_x, x_dtype, nfr, h_wind, nwind, hop, h_fb, nband, cep_mode, d_spec, d_cep, s, kernels);
 }

@@ -2304,6 +2304,74 @@ extern "C" int64_t pvx_filterbank(const void* x, int x_dtype, int64_t n, const d
     return nfr;
 }
 
+// ---- windowed spectral measures (k_specdesc.hip) ------------------------------------------------
+static thread_local const char* t_specdesc_kernels = "";
+extern "C" const char* pvx_specdesc_last_kernels(void) { return t_specdesc_kernels; }
+
+// frames read: 0 .. nfr - 1, and frame nfr too for the flux
+static int specdesc_args(int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int measure, const double* a,
+                         const double* b, const double* out) {
+    if (n < 0 || !wind || nwind < 2 || hop < 1 || nfr < 0) { pvx_set_error("bad pvx_specdesc argument"); return PVX_ERR_INVALID; }
+    if (x_dtype != PVX_F32 && x_dtype != PVX_F64 && x_dtype != PVX_I16) { pvx_set_error("bad x_dtype %d", x_dtype); return PVX_ERR_INVALID; }
+    if (measure < PVX_SD_RATIO || measure > PVX_SD_PSD) { pvx_set_error("pvx_specdesc: unknown measure %d", measure); return PVX_ERR_INVALID; }
+    if ((measure != PVX_SD_PSD && !a) || (measure == PVX_SD_RATIO && !b)) { pvx_set_error("pvx_specdesc: null weights"); return PVX_ERR_INVALID; }
+    const int64_t last = measure == PVX_SD_FLUX ? nfr : nfr - 1;
+    if (nfr > 0 && (last > (INT64_MAX - nwind) / hop || last * hop + nwind > n)) {
+        pvx_set_error("pvx_specdesc: frame %lld of %d samples at hop %d ends beyond the %lld samples of the signal", (long long)last, nwind, hop,
+                      (long long)n);
+        return PVX_ERR_SIZE;
+    }
+    if (nfr > 0 && !out) { pvx_set_error("null pvx_specdesc output"); return PVX_ERR_INVALID; }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_specdesc_dev(const void* d_x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int measure,
+                                    const double* a, const double* b, double* d_out, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = specdesc_args(x_dtype, n, wind, nwind, hop, nfr, measure, a, b, d_out)) != PVX_OK) return rc;
+    t_specdesc_kernels = "";
+    if (nfr == 0) return 0;
+    if (!d_x) { pvx_set_error("null pvx_specdesc signal"); return PVX_ERR_INVALID; }
+    if ((rc = pvx_specdesc_run(d_x, x_dtype, nfr, wind, nwind, hop, measure, a, b, d_out, true, nfr, (hipStream_t)stream,
+                               &t_specdesc_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nfr;
+}
+
+extern "C" int64_t pvx_specdesc(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int measure,
+                                const double* a, const double* b, double* out) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = specdesc_args(x_dtype, n, wind, nwind, hop, nfr, measure, a, b, out)) != PVX_OK) return rc;
+    t_specdesc_kernels = "";
+    if (nfr == 0) return 0;
+    if (!x) { pvx_set_error("null pvx_specdesc signal"); return PVX_ERR_INVALID; }
+    // a chunk of values needs its own samples only (a flux chunk: one frame more); the periodogram's chunks are whole
+    // blocks, so that the block sums -- and with them the bits -- are those of the unchunked call
+    size_t limit = (size_t)2 << 30;                                   // per buffer
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
+    const size_t es = dtype_size(x_dtype);
+    const bool psd = measure == PVX_SD_PSD;
+    const int64_t extra = measure == PVX_SD_FLUX ? 1 : 0;
+    const int64_t room = (int64_t)(limit / es);                       // samples
+    int64_t fc = room > nwind + extra * hop ? (room - nwind) / hop + 1 - extra : 1;
+    fc = std::min<int64_t>(fc, std::max<int64_t>(1, (int64_t)(limit / 8)));
+    if (psd) fc = std::max<int64_t>(fc - fc % PVX_SPECDESC_BLOCK, PVX_SPECDESC_BLOCK);
+    fc = std::min(fc, nfr);
+    DevMem dx, dout;
+    if ((rc = dx.alloc((size_t)((fc - 1 + extra) * hop + nwind) * es)) != PVX_OK ||
+        (rc = dout.alloc((size_t)(psd ? nwind / 2 : fc) * 8)) != PVX_OK) return rc;
+    for (int64_t f0 = 0; f0 < nfr; f0 += fc) {
+        const int64_t cnt = std::min(fc, nfr - f0);
+        if ((rc = host_to_device(dx.get(), (const char*)x + (size_t)(f0 * hop) * es, (size_t)((cnt - 1 + extra) * hop + nwind) * es)) != PVX_OK) return rc;
+        if ((rc = pvx_specdesc_run(dx.get(), x_dtype, cnt, wind, nwind, hop, measure, a, b, dout.as<double>(), f0 == 0,
+                                   f0 + cnt == nfr ? nfr : 0, nullptr, &t_specdesc_kernels)) != PVX_OK) return rc;
+        if (!psd && (rc = device_to_host((char*)out + (size_t)f0 * 8, dout.get(), (size_t)cnt * 8)) != PVX_OK) return rc;
+    }
+    if (psd && (rc = device_to_host(out, dout.get(), (size_t)(nwind / 2) * 8)) != PVX_OK) return rc;
+    return nfr;
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

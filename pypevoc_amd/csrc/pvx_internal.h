@@ -336,6 +336,13 @@ int pvx_period_run(PeriodParams p, const double* h_wind, const int64_t* h_idx, h
 int pvx_fbank_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_wind, int nwind, int hop, const double* h_fb, int nband,
                   int cep_mode, double* d_spec, double* d_cep, hipStream_t s, const char** kernels);
 
+// windowed spectral measures (k_specdesc.hip; include/pvx.h: pvx_specdesc): nfr values (PSD: frames) of the device signal d_x.
+// The window and the weights h_a / h_b [nwind/2 + 1] are host arrays, d_out device memory.  PSD: d_out [nwind/2] carries the
+// running sum between the calls of one signal: `first` starts it from zero, total > 0 marks the last call and divides by it;
+// the calls before the last one take whole blocks of PVX_SPECDESC_BLOCK frames.  Synchronises the stream.
+int pvx_specdesc_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_wind, int nwind, int hop, int meas, const double* h_a,
+                     const double* h_b, double* d_out, bool first, int64_t total, hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)

@@ -1,0 +1,5 @@
+"""Drop-in for pypevoc/speech: the analysis functions, under both names the reference's package gives them
+(pypevoc/speech/__init__.py:3: `analysis`).  Its segmenter classes are not mirrored."""
+from . import SpeechAnalysis  # noqa: F401
+
+analysis = SpeechAnalysis
