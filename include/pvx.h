@@ -489,6 +489,36 @@ int64_t pvx_specdesc_dev(const void* d_x, int x_dtype, int64_t n, const double* 
                          int measure, const double* a, const double* b, double* d_out, void* stream);
 const char* pvx_specdesc_last_kernels(void);
 
+/* ---- Welch-averaged cross and auto spectra, block by block (pypevoc/TransferFunctions.py: transferogram :112-185,
+ *      tfe :21-26; matplotlib.mlab's csd / psd / cohere behind them) ----
+ *
+ * Block b = 0 .. nblk - 1 starts at sample start + b*delta of x and of y, its segment s = 0 .. nseg - 1 at s*step further on.
+ * With X_s = rfft(x[.. : .. + nwind] * wind) and Y_s likewise, for the bins k = 0 .. nwind/2 (the Nyquist bin included):
+ *   sxy[b][k] = (1/nseg) sum_s conj(Y_s[k]) X_s[k]      [nblk][nwind/2 + 1] complex (re, im)
+ *   sxx[b][k] = (1/nseg) sum_s |X_s[k]|^2               [nblk][nwind/2 + 1]
+ *   syy[b][k] = (1/nseg) sum_s |Y_s[k]|^2               [nblk][nwind/2 + 1]
+ * unscaled means: the one-sided factor, Fs and sum(wind^2) of a density, the ratios of a transfer function and of a
+ * coherence are the caller's.  y null: the auto spectrum of x alone (sxy, syy unused and may be null; the second
+ * transform is skipped).  wind: host array [nwind], the bare window.  nblk, nseg, step, delta are the caller's; the last
+ * sample read, start + (nblk-1)*delta + (nseg-1)*step + nwind - 1, must lie inside n (the length of x and of y), else
+ * PVX_ERR_SIZE.  nblk = 0: nothing is launched, the outputs are untouched.
+ * x, y: float32, float64 or int16 samples (pvx_dtype, one type for both), widened on load; all arithmetic float64.  A
+ * bin of a block is one lane's sum, the block's segments added in index order (no atomics): a block's values do not depend
+ * on the grid, on the other blocks of the call or on where the samples came from.  nwind 512 / 1024 / 2048 run one fused kernel, any
+ * other nwind k_frames + rocFFT + one kernel per batch of whole blocks; PVX_XSPEC_ROWS in the environment sends every nwind
+ * down the rows route.  Host input is chunked by PVX_MAX_DEVICE_BYTES in whole blocks (at least one), both signals cut at
+ * the same samples.  pvx_xspec_dev: x, y and the outputs are device memory (wind stays a host array), work on `stream`,
+ * synchronised before the return.  Both return nblk or a negative status; calls share the filter banks' per-device
+ * workspace and take turns on it.  pvx_xspec_last_kernels: what the calling thread's last call ran
+ * ("k_xspec_fused<1024>", "k_frames+rocfft+k_xspec_rows"; "" when it had no block).
+ */
+int64_t pvx_xspec(const void* x, const void* y, int x_dtype, int64_t n, const double* wind, int nwind, int step, int64_t start,
+                  int64_t delta, int64_t nblk, int nseg, double* sxy, double* sxx, double* syy);
+int64_t pvx_xspec_dev(const void* d_x, const void* d_y, int x_dtype, int64_t n, const double* wind, int nwind, int step,
+                      int64_t start, int64_t delta, int64_t nblk, int nseg, double* d_sxy, double* d_sxx, double* d_syy,
+                      void* stream);
+const char* pvx_xspec_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

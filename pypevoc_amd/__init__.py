@@ -15,9 +15,10 @@ from .Periodicity import (PeriodSeries, PeriodTimeSeries, period_marks_corr,  # 
 from .FFTFilters import FilterBank, TriangularFilterBank, MelFilterBank, PiecewiseFilterSpec  # noqa: F401
 from . import FFTFilters  # noqa: F401  (`from pypevoc_amd import FFTFilters as ft`, as the reference's examples import it)
 from .Heterodyne import HeterodyneHarmonic, heterodyne  # noqa: F401
+from . import TransferFunctions  # noqa: F401  (`from pypevoc_amd import TransferFunctions`, as `from pypevoc import TransferFunctions`)
 from ._lib import PvxError  # noqa: F401
 
 __all__ = ["PV", "PVHarmonic", "SinSum", "RegPartial", "PeakFinder", "PVBatch", "PVMany", "PvxError",
            "PeriodSeries", "PeriodTimeSeries", "period_marks_corr", "period_marks_peak", "period_marks_amdf",
            "FilterBank", "TriangularFilterBank", "MelFilterBank", "PiecewiseFilterSpec", "FFTFilters",
-           "HeterodyneHarmonic", "heterodyne"]
+           "HeterodyneHarmonic", "heterodyne", "TransferFunctions"]

@@ -142,6 +142,11 @@ SIGNATURES = {
     "pvx_specdesc_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                           ctypes.c_int, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvx_specdesc_last_kernels": (ctypes.c_char_p, []),
+    "pvx_xspec": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    "pvx_xspec_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "pvx_xspec_last_kernels": (ctypes.c_char_p, []),
 }
 
 

@@ -2372,6 +2372,84 @@ extern "C" int64_t pvx_specdesc(const void* x, int x_dtype, int64_t n, const dou
     return nfr;
 }
 
+// ---- cross and auto spectra block by block (k_xspec.hip) ---------------------------------------
+static thread_local const char* t_xspec_kernels = "";
+extern "C" const char* pvx_xspec_last_kernels(void) { return t_xspec_kernels; }
+
+// samples read: start .. start + (nblk-1)*delta + (nseg-1)*step + nwind - 1
+static int xspec_args(const void* y, int x_dtype, int64_t n, const double* wind, int nwind, int step, int64_t start, int64_t delta,
+                      int64_t nblk, int nseg, const double* sxy, const double* sxx, const double* syy) {
+    if (n < 0 || !wind || nwind < 2 || step < 1 || start < 0 || delta < 1 || nblk < 0 || nseg < 1) {
+        pvx_set_error("bad pvx_xspec argument");
+        return PVX_ERR_INVALID;
+    }
+    if (x_dtype != PVX_F32 && x_dtype != PVX_F64 && x_dtype != PVX_I16) { pvx_set_error("bad x_dtype %d", x_dtype); return PVX_ERR_INVALID; }
+    if (nblk > 0) {
+        const __int128 end = (__int128)start + (__int128)(nblk - 1) * delta + (__int128)(nseg - 1) * step + nwind;
+        if (end > (__int128)n) {
+            pvx_set_error("pvx_xspec: block %lld (%d segments of %d samples at step %d, blocks %lld apart from %lld) ends beyond the %lld samples of the signals",
+                          (long long)(nblk - 1), nseg, nwind, step, (long long)delta, (long long)start, (long long)n);
+            return PVX_ERR_SIZE;
+        }
+        if ((__int128)nblk * (nwind / 2 + 1) > ((__int128)1 << 56)) { pvx_set_error("pvx_xspec: too many blocks"); return PVX_ERR_INVALID; }
+        if (!sxx || (y && (!sxy || !syy))) { pvx_set_error("null pvx_xspec output"); return PVX_ERR_INVALID; }
+    }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_xspec_dev(const void* d_x, const void* d_y, int x_dtype, int64_t n, const double* wind, int nwind, int step,
+                                 int64_t start, int64_t delta, int64_t nblk, int nseg, double* d_sxy, double* d_sxx, double* d_syy,
+                                 void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = xspec_args(d_y, x_dtype, n, wind, nwind, step, start, delta, nblk, nseg, d_sxy, d_sxx, d_syy)) != PVX_OK) return rc;
+    t_xspec_kernels = "";
+    if (nblk == 0) return 0;
+    if (!d_x) { pvx_set_error("null pvx_xspec signal"); return PVX_ERR_INVALID; }
+    const size_t es = dtype_size(x_dtype);
+    if ((rc = pvx_xspec_run((const char*)d_x + (size_t)start * es, d_y ? (const char*)d_y + (size_t)start * es : nullptr, x_dtype, wind, nwind,
+                            step, delta, nblk, nseg, d_sxy, d_sxx, d_syy, (hipStream_t)stream, &t_xspec_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nblk;
+}
+
+extern "C" int64_t pvx_xspec(const void* x, const void* y, int x_dtype, int64_t n, const double* wind, int nwind, int step, int64_t start,
+                             int64_t delta, int64_t nblk, int nseg, double* sxy, double* sxx, double* syy) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = xspec_args(y, x_dtype, n, wind, nwind, step, start, delta, nblk, nseg, sxy, sxx, syy)) != PVX_OK) return rc;
+    t_xspec_kernels = "";
+    if (nblk == 0) return 0;
+    if (!x) { pvx_set_error("null pvx_xspec signal"); return PVX_ERR_INVALID; }
+    // a chunk is whole blocks with the samples they read, the same cut for both signals: a block's bits are those of the
+    // unchunked call
+    size_t limit = (size_t)2 << 30;                                   // per buffer
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
+    const size_t es = dtype_size(x_dtype);
+    const int64_t nhalf = nwind / 2 + 1;
+    const int64_t span = (int64_t)(nseg - 1) * step + nwind;          // samples of a block
+    const int64_t room = (int64_t)(limit / es);
+    int64_t bc = room > span ? (room - span) / delta + 1 : 1;
+    bc = std::min<int64_t>(bc, std::max<int64_t>(1, (int64_t)(limit / ((size_t)nhalf * 16))));
+    bc = std::min(bc, nblk);
+    const size_t chunk_samples = (size_t)((bc - 1) * delta + span);
+    DevMem dx, dy, dxy, dxx, dyy;
+    if ((rc = dx.alloc(chunk_samples * es)) != PVX_OK || (rc = dxx.alloc((size_t)(bc * nhalf) * 8)) != PVX_OK) return rc;
+    if (y && ((rc = dy.alloc(chunk_samples * es)) != PVX_OK || (rc = dxy.alloc((size_t)(bc * nhalf) * 16)) != PVX_OK ||
+              (rc = dyy.alloc((size_t)(bc * nhalf) * 8)) != PVX_OK)) return rc;
+    for (int64_t b0 = 0; b0 < nblk; b0 += bc) {
+        const int64_t cnt = std::min(bc, nblk - b0);
+        const size_t off = (size_t)(start + b0 * delta) * es, bytes = (size_t)((cnt - 1) * delta + span) * es;
+        if ((rc = host_to_device(dx.get(), (const char*)x + off, bytes)) != PVX_OK) return rc;
+        if (y && (rc = host_to_device(dy.get(), (const char*)y + off, bytes)) != PVX_OK) return rc;
+        if ((rc = pvx_xspec_run(dx.get(), y ? dy.get() : nullptr, x_dtype, wind, nwind, step, delta, cnt, nseg, dxy.as<double>(), dxx.as<double>(),
+                                dyy.as<double>(), nullptr, &t_xspec_kernels)) != PVX_OK) return rc;
+        if ((rc = device_to_host((char*)sxx + (size_t)(b0 * nhalf) * 8, dxx.get(), (size_t)(cnt * nhalf) * 8)) != PVX_OK) return rc;
+        if (y && ((rc = device_to_host((char*)syy + (size_t)(b0 * nhalf) * 8, dyy.get(), (size_t)(cnt * nhalf) * 8)) != PVX_OK ||
+                  (rc = device_to_host((char*)sxy + (size_t)(b0 * nhalf) * 16, dxy.get(), (size_t)(cnt * nhalf) * 16)) != PVX_OK)) return rc;
+    }
+    return nblk;
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

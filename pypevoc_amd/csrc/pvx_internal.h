@@ -343,6 +343,12 @@ int pvx_fbank_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_win
 int pvx_specdesc_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_wind, int nwind, int hop, int meas, const double* h_a,
                      const double* h_b, double* d_out, bool first, int64_t total, hipStream_t s, const char** kernels);
 
+// Welch-averaged cross and auto spectra, block by block (k_xspec.hip; include/pvx.h: pvx_xspec): nblk blocks of nseg segments
+// of the device signals d_x, d_y (d_y null: the auto spectrum of d_x alone), which point at the first block's first sample.
+// The window is a host array, the outputs device memory ([nblk][nwind/2 + 1], d_sxy complex).  Synchronises the stream.
+int pvx_xspec_run(const void* d_x, const void* d_y, int x_dtype, const double* h_wind, int nwind, int step, int64_t delta, int64_t nblk,
+                  int nseg, double* d_sxy, double* d_sxx, double* d_syy, hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)
