@@ -4,7 +4,9 @@
 
 Run in the build container only (the reference never travels to the GPU box):
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_period.py
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_period.py [P9 ...]
+
+(with names: only the fixtures that start with one of them are written).
 
 The prefix is P: tests/conftest.py's golden_names() picks up every G* / H* file for the phase-vocoder
 tests.  Each file holds one signal (float32-exact signals as float32; P6 reads G7's Perlman samples) and
@@ -97,7 +99,14 @@ def run(x, name, ctor, window=None, mode="calc", calc=None, pbp=None, index=None
     return meta
 
 
+def wanted(fname):
+    """Every fixture, or only those whose names start with a command-line argument (`... make_golden_period.py P9`)."""
+    return not sys.argv[1:] or fname.startswith(tuple(sys.argv[1:]))
+
+
 def save(fname, x, sr, runs, arrays, x_store=None):
+    if not wanted(fname):
+        return
     out = dict(arrays)
     out["x"] = x.astype(np.float32) if x_store is None else x_store
     out["sr"] = np.float64(sr)
@@ -179,8 +188,9 @@ def main():
     out["sr"] = np.float64(sr6)
     out["x_from"] = np.array("G7_perlman")
     out["runs"] = np.array(json.dumps(runs))
-    np.savez_compressed(os.path.join(HERE, "P6_perlman.npz"), **out)
-    print("P6_perlman", len(runs), "runs")
+    if wanted("P6_perlman"):
+        np.savez_compressed(os.path.join(HERE, "P6_perlman.npz"), **out)
+        print("P6_perlman", len(runs), "runs")
 
     # P8a -- a frame beyond the LDS (nwind 8192 > 6144) whose first negative correlation lag lies past maxdelay (960):
     # a 3 Hz swell under a 150 Hz tone, seen through a window whose first half is zero.  Frames where the swell is
@@ -211,6 +221,29 @@ def main():
     runs.append(run(x7, "pbp_f", {"sr": sr}, mode="pbp", pbp={"tf": tf, "f": f}, arrays=arrays))
     runs.append(run(x7, "pbp_amdf_thr", {"sr": sr, "method": "amdf"}, mode="pbp", pbp={"threshold": 0.5}, arrays=arrays))
     save("P7_period_by_period", x7, sr, runs, arrays)
+
+    # P9 -- the threshold cases PeakFinder documents and odd windows, 8 kHz, harmonics of a 220 Hz vibrato plus noise at 5 %
+    # of the fundamental: threshold 0 (falls back to min(y)); threshold -1 < min(y) (th < 0: non-maxima are admitted with
+    # score 0, lowest index first -- the only exact score ties); ncand 1 and 64; hanning(481), under which amdf's peaks stay
+    # below 0.5, hence threshold 0.3; a 479-sample window with maxdelay 478 = nwind - 1 (no multiple of 4: the last lags
+    # have one or two terms)
+    sr9 = 8000
+    t9 = np.arange(int(0.5 * sr9)) / float(sr9)
+    ph9 = 2 * np.pi * np.cumsum(220.0 * (1.0 + 0.03 * np.sin(2 * np.pi * 3.0 * t9))) / sr9
+    x9 = sum(0.5 / h * np.sin(h * ph9) for h in range(1, 7)) + 0.05 * 0.5 * np.random.default_rng(9).standard_normal(len(t9))
+    x9 = x9.astype(np.float32).astype(np.float64)
+    arrays, runs = {}, []
+    base = {"sr": sr9, "fmax": 1000}
+    for m in METHODS:
+        for c in CAND:
+            runs.append(run(x9, "thr0_%s_%s" % (m, c), dict(base, threshold=0, method=m, cand_method=c), arrays=arrays))
+            runs.append(run(x9, "thneg_%s_%s" % (m, c), dict(base, threshold=-1.0, method=m, cand_method=c), arrays=arrays))
+        # (one candidate, or the same candidates whatever cand_method: 'fft', whose bin count and row stride hold n / 2)
+        runs.append(run(x9, "ncand1_" + m, dict(base, ncand=1, method=m), arrays=arrays))
+        runs.append(run(x9, "ncand64_" + m, dict(base, ncand=64, method=m), arrays=arrays))
+        runs.append(run(x9, "odd481_" + m, dict(base, threshold=0.3, method=m), window=np.hanning(481), arrays=arrays))
+        runs.append(run(x9, "w479_" + m, dict(base, fmin=16.72, method=m), window=479, arrays=arrays))
+    save("P9_thresholds_odd", x9, sr9, runs, arrays)
 
 
 if __name__ == "__main__":
