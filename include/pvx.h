@@ -37,7 +37,8 @@ typedef enum {
     PVX_ERR_HIP = -3,         /* a HIP or rocFFT call failed */
     PVX_ERR_ALLOC = -4,       /* device or host allocation failed */
     PVX_ERR_UNSUPPORTED = -5, /* valid request outside what the kernels handle */
-    PVX_ERR_SIZE = -6         /* caller buffer too small / wrong length */
+    PVX_ERR_SIZE = -6,        /* caller buffer too small / wrong length */
+    PVX_ERR_SINGULAR = -7     /* a frame's Toeplitz system has a zero prediction error (pvx_lpc, pvx_iaif) */
 } pvx_status;
 
 /* sample types accepted for the input signal x (PV.py:84 copies whatever the caller passed) */
@@ -518,6 +519,57 @@ int64_t pvx_xspec_dev(const void* d_x, const void* d_y, int x_dtype, int64_t n, 
                       int64_t start, int64_t delta, int64_t nblk, int nseg, double* d_sxy, double* d_sxx, double* d_syy,
                       void* stream);
 const char* pvx_xspec_last_kernels(void);
+
+/* ---- linear prediction and glottal inverse filtering (pypevoc/speech/glottal.py: lpc :32-34, iaif_ola :36-84,
+ *      InverseFilter.apply :190-234; pypevoc/speech/SpeechAnalysis.py: lpc :9-24) ----
+ *
+ * pvx_lpc: coef[i] = [1, a_1 .. a_order] of the frames v_i = x[i*hop : i*hop+nwind] * wind (wind NULL: the bare frame):
+ * r[k] = sum_j v[j+k] v[j], k <= order, and toeplitz(r[:order]) a = -r[1:] by Levinson-Durbin (scipy's solve_toeplitz).
+ * coef [nfr][order+1].  0 <= order <= PVX_LPC_MAX_ORDER, 1 <= nwind <= PVX_LPC_MAX_NWIND, else PVX_ERR_UNSUPPORTED.
+ *
+ * pvx_iaif: Alku's iterative adaptive inverse filtering of the frames x[i*hop : i*hop+nwind], i < nfr, as
+ * InverseFilter.apply computes it (GLOTTAL.md restates the steps): the high-pass FIR hp_b [ntaps] with its
+ * round_half_even(ntaps/2 - 1) samples of delay removed, the ramp of tract_order + 1 samples in front of the frame, a
+ * first-order LPC, n_it rounds of vocal-tract (tract_order) and glottal (glottal_order) LPC, inverse FIR and leaky
+ * integration (v[j] += leak * v[j-1]), and the final vocal-tract pass.  lpc_wind [nwind] windows the vectors the LPCs
+ * see.  Outputs, each of them nullable:
+ *   g, dg   [nfr][nwind]  the frames' glottal flow and its derivative
+ *   vt      [nfr][tract_order+1]  the last vocal-tract filter of each frame
+ *   gc      [nfr][glottal_order+1]  the last glottal filter; n_it = 0: [nfr][2], the first-order one
+ *   glot, dglot [n]  the overlap-add of g * ola_wind and dg * ola_wind (ola_wind [nwind], needed for these two only),
+ *           divided by the sum of the windows where that sum is > 0; a sample adds its frames in ascending order
+ * nfr is the caller's (iaif_ola: pvx_nframes(n, nwind, hop)); the last sample read, (nfr-1)*hop + nwind - 1, must lie
+ * inside n, else PVX_ERR_SIZE.  nfr = 0: nothing is launched, glot and dglot are zeroed.  Limits (compile time):
+ * 2 <= nwind <= PVX_IAIF_MAX_NWIND, 1 <= ntaps <= PVX_IAIF_MAX_TAPS, orders 0 .. PVX_LPC_MAX_ORDER, n_it >= 0; beyond
+ * them PVX_ERR_UNSUPPORTED and no launch.
+ *
+ * Both: x float32, float64 or int16 samples (pvx_dtype), widened on load; all arithmetic float64, every sum in a fixed
+ * order: a value does not depend on the grid, on the other frames of the call or on where the samples came from.  A
+ * frame whose Levinson recursion meets a prediction error of exactly 0 (a silent frame: the reference raises LinAlgError
+ * "Singular principal minor") makes the call return PVX_ERR_SINGULAR with the first such frame in *singular_frame
+ * (nullable; -1 otherwise); the outputs are then unspecified.  Host input is processed in chunks of whole frames sized
+ * by PVX_MAX_DEVICE_BYTES (per buffer; default 256 MiB), a chunk recomputing the frames that overlap its first and last
+ * output samples: the bits do not depend on the chunking.  The _dev forms take device memory for x and every output
+ * (hp_b and the windows stay host arrays), group their frames the same way, work on `stream` and are synchronised
+ * before they return.  All four return nfr or a negative status.  pvx_iaif_last_kernels: what the calling thread's last
+ * pvx_iaif / pvx_lpc call ran ("k_iaif_frames+k_iaif_ola", "k_iaif_frames", "k_lpc_frames"; "" when it had no frame).
+ */
+#define PVX_LPC_MAX_ORDER 128
+#define PVX_LPC_MAX_NWIND 16384
+#define PVX_IAIF_MAX_NWIND 4096
+#define PVX_IAIF_MAX_TAPS 4095
+int64_t pvx_lpc(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int order, double* coef,
+                int64_t* singular_frame);
+int64_t pvx_lpc_dev(const void* d_x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int order,
+                    double* d_coef, int64_t* singular_frame, void* stream);
+int64_t pvx_iaif(const void* x, int x_dtype, int64_t n, int nwind, int hop, int64_t nfr, const double* hp_b, int ntaps,
+                 const double* lpc_wind, const double* ola_wind, int tract_order, int glottal_order, double leak, int n_it,
+                 double* glot, double* dglot, double* g, double* dg, double* vt, double* gc, int64_t* singular_frame);
+int64_t pvx_iaif_dev(const void* d_x, int x_dtype, int64_t n, int nwind, int hop, int64_t nfr, const double* hp_b, int ntaps,
+                     const double* lpc_wind, const double* ola_wind, int tract_order, int glottal_order, double leak, int n_it,
+                     double* d_glot, double* d_dglot, double* d_g, double* d_dg, double* d_vt, double* d_gc,
+                     int64_t* singular_frame, void* stream);
+const char* pvx_iaif_last_kernels(void);
 
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("PVX_LIB") or os.path.join(_HERE, "libpvx_hip.so")   #
 PVX_SYNTH_NO_PHCOR = 1
 PVX_SYNTH_F32 = 2
 PVX_ERR_SIZE = -6            # include/pvx.h
+PVX_ERR_UNSUPPORTED = -5
+PVX_ERR_SINGULAR = -7
 PVX_F32, PVX_F64, PVX_I16 = 0, 1, 2
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -147,6 +149,17 @@ SIGNATURES = {
     "pvx_xspec_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4),
     "pvx_xspec_last_kernels": (ctypes.c_char_p, []),
+    "pvx_lpc": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                 ctypes.c_int, c_double_p, c_int64_p]),
+    "pvx_lpc_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                     ctypes.c_int, ctypes.c_void_p, c_int64_p, ctypes.c_void_p]),
+    "pvx_iaif": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p,
+                                  ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int] +
+                 [c_double_p] * 6 + [c_int64_p]),
+    "pvx_iaif_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p,
+                                      ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int] +
+                     [ctypes.c_void_p] * 6 + [c_int64_p, ctypes.c_void_p]),
+    "pvx_iaif_last_kernels": (ctypes.c_char_p, []),
 }
 
 

@@ -2450,6 +2450,191 @@ extern "C" int64_t pvx_xspec(const void* x, const void* y, int x_dtype, int64_t 
     return nblk;
 }
 
+// ---- linear prediction and glottal inverse filtering (k_iaif.hip) -------------------------------
+static thread_local const char* t_iaif_kernels = "";
+extern "C" const char* pvx_iaif_last_kernels(void) { return t_iaif_kernels; }
+
+static size_t iaif_limit() {
+    size_t limit = (size_t)256 << 20;                                 // per buffer
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
+    return limit;
+}
+
+// frames read: 0 .. nfr - 1
+static int lpc_frames_args(const char* what, int x_dtype, int64_t n, int nwind, int hop, int64_t nfr) {
+    if (n < 0 || nwind < 1 || hop < 1 || nfr < 0) { pvx_set_error("bad %s argument", what); return PVX_ERR_INVALID; }
+    if (x_dtype != PVX_F32 && x_dtype != PVX_F64 && x_dtype != PVX_I16) { pvx_set_error("bad x_dtype %d", x_dtype); return PVX_ERR_INVALID; }
+    if (nfr > 0 && (nfr - 1 > (INT64_MAX - nwind) / hop || (nfr - 1) * hop + nwind > n)) {
+        pvx_set_error("%s: frame %lld of %d samples at hop %d ends beyond the %lld samples of the signal", what, (long long)(nfr - 1), nwind, hop,
+                      (long long)n);
+        return PVX_ERR_SIZE;
+    }
+    return PVX_OK;
+}
+
+// rows of `bytes` each from a device buffer to the caller's: on the stream (DEV), or to the host before the return
+template <bool DEV> static int rows_out(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    if (!dst || bytes == 0) return PVX_OK;
+    if (!DEV) return device_to_host(dst, src, bytes);
+    PVX_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+    return PVX_OK;
+}
+template <bool DEV> static int zero_out(double* dst, int64_t count, hipStream_t s) {
+    if (!dst || count <= 0) return PVX_OK;
+    if (!DEV) { memset(dst, 0, (size_t)count * 8); return PVX_OK; }
+    PVX_HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)count * 8, s));
+    return PVX_OK;
+}
+
+// Frames in groups of `own`: a group computes its own frames and, for an overlap-add, the `ov` frames before them that reach
+// into its first output samples (frames only reach forwards: none after them does).  A frame's values do not depend on its
+// group, a sample adds its frames in ascending order whatever the group: the bits are those of one group.
+template <bool DEV>
+static int64_t iaif_body(const void* x, int x_dtype, int64_t n, int nwind, int hop, int64_t nfr, const double* hp_b, int ntaps,
+                         const double* lpc_wind, const double* ola_wind, int pt, int pg, double leak, int n_it, double* glot, double* dglot,
+                         double* g, double* dg, double* vt, double* gc, int64_t* singular_frame, hipStream_t s) {
+    if (singular_frame) *singular_frame = -1;
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_iaif_kernels = "";
+    if ((rc = lpc_frames_args("pvx_iaif", x_dtype, n, nwind, hop, nfr)) != PVX_OK) return rc;
+    const bool ola = glot || dglot;
+    if (!hp_b || !lpc_wind || (ola && !ola_wind) || nwind < 2 || ntaps < 1 || pt < 0 || pg < 0 || n_it < 0) {
+        pvx_set_error("bad pvx_iaif argument");
+        return PVX_ERR_INVALID;
+    }
+    if (nwind > PVX_IAIF_MAX_NWIND || ntaps > PVX_IAIF_MAX_TAPS || pt > PVX_LPC_MAX_ORDER || pg > PVX_LPC_MAX_ORDER) {
+        pvx_set_error("pvx_iaif: nwind %d, %d taps, orders %d / %d: the kernel takes nwind <= %d, <= %d taps, orders <= %d", nwind, ntaps, pt, pg,
+                      PVX_IAIF_MAX_NWIND, PVX_IAIF_MAX_TAPS, PVX_LPC_MAX_ORDER);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    if (nfr == 0) {
+        if ((rc = zero_out<DEV>(glot, n, s)) != PVX_OK || (rc = zero_out<DEV>(dglot, n, s)) != PVX_OK) return rc;
+        if (DEV) PVX_HIP_CHECK(hipStreamSynchronize(s));
+        return 0;
+    }
+    if (!x) { pvx_set_error("null pvx_iaif signal"); return PVX_ERR_INVALID; }
+    const size_t es = dtype_size(x_dtype), limit = iaif_limit();
+    const int64_t ov = ola ? (nwind - 1 + hop - 1) / hop : 0;
+    int64_t cap = std::max<int64_t>(1, (int64_t)(limit / ((size_t)nwind * 8)));                 // rows of g / dg
+    cap = std::min<int64_t>(cap, (int64_t)(limit / es) > nwind ? ((int64_t)(limit / es) - nwind) / hop + 1 : 1);   // frames of samples
+    const int64_t own = std::min(nfr, std::max<int64_t>(1, cap - ov));
+    const int64_t rows = std::min(nfr, own + ov);
+    const int gcw = (n_it > 0 ? pg : 1) + 1;
+    DevMem dx, wg, wdg, wvt, wgc, og, odg;
+    if ((rc = wg.alloc((size_t)rows * nwind * 8)) != PVX_OK || (rc = wdg.alloc((size_t)rows * nwind * 8)) != PVX_OK ||
+        (rc = wvt.alloc((size_t)rows * (pt + 1) * 8)) != PVX_OK || (rc = wgc.alloc((size_t)rows * gcw * 8)) != PVX_OK) return rc;
+    if (!DEV) {
+        if ((rc = dx.alloc((size_t)((rows - 1) * hop + nwind) * es)) != PVX_OK) return rc;
+        if (glot && (rc = og.alloc((size_t)(own * hop + nwind) * 8)) != PVX_OK) return rc;
+        if (dglot && (rc = odg.alloc((size_t)(own * hop + nwind) * 8)) != PVX_OK) return rc;
+    }
+    const IaifCall call = {x_dtype, nwind, hop, ntaps, pt, pg, n_it, leak, hp_b, lpc_wind, ola_wind};
+    const int64_t cover = (nfr - 1) * hop + nwind;                    // the samples beyond the last frame stay zero
+    for (int64_t o0 = 0; o0 < nfr; o0 += own) {
+        const int64_t o1 = std::min(nfr, o0 + own);
+        const int64_t s0 = o0 * hop, s1 = o1 == nfr ? cover : o1 * hop;
+        const int64_t lo = s0 - nwind + 1;
+        const int64_t fa = ola ? (lo <= 0 ? 0 : (lo + hop - 1) / hop) : o0, nf = o1 - fa;
+        const void* cx = (const char*)x + (size_t)(fa * hop) * es;
+        if (!DEV) {
+            if ((rc = host_to_device(dx.get(), cx, (size_t)((nf - 1) * hop + nwind) * es)) != PVX_OK) return rc;
+            cx = dx.get();
+        }
+        double* pgl = glot ? (DEV ? glot + s0 : og.as<double>()) : nullptr;
+        double* pdg = dglot ? (DEV ? dglot + s0 : odg.as<double>()) : nullptr;
+        int64_t sing = -1;
+        if ((rc = pvx_iaif_run(call, cx, fa, nf, wg.as<double>(), wdg.as<double>(), wvt.as<double>(), wgc.as<double>(), s0, s1 - s0, pgl, pdg,
+                               &sing, s, &t_iaif_kernels)) != PVX_OK) return rc;   // synchronises the stream
+        if (sing >= 0) {
+            if (singular_frame) *singular_frame = fa + sing;
+            pvx_set_error("pvx_iaif: frame %lld: Singular principal minor (a prediction error of exactly 0)", (long long)(fa + sing));
+            return PVX_ERR_SINGULAR;
+        }
+        const size_t r0 = (size_t)(o0 - fa), cnt = (size_t)(o1 - o0);
+        if ((rc = rows_out<DEV>(g ? g + (size_t)o0 * nwind : nullptr, wg.as<double>() + r0 * nwind, cnt * nwind * 8, s)) != PVX_OK ||
+            (rc = rows_out<DEV>(dg ? dg + (size_t)o0 * nwind : nullptr, wdg.as<double>() + r0 * nwind, cnt * nwind * 8, s)) != PVX_OK ||
+            (rc = rows_out<DEV>(vt ? vt + (size_t)o0 * (pt + 1) : nullptr, wvt.as<double>() + r0 * (pt + 1), cnt * (pt + 1) * 8, s)) != PVX_OK ||
+            (rc = rows_out<DEV>(gc ? gc + (size_t)o0 * gcw : nullptr, wgc.as<double>() + r0 * gcw, cnt * gcw * 8, s)) != PVX_OK) return rc;
+        if (!DEV) {
+            if ((rc = rows_out<false>(glot ? glot + s0 : nullptr, og.get(), (size_t)(s1 - s0) * 8, s)) != PVX_OK ||
+                (rc = rows_out<false>(dglot ? dglot + s0 : nullptr, odg.get(), (size_t)(s1 - s0) * 8, s)) != PVX_OK) return rc;
+        }
+    }
+    if ((rc = zero_out<DEV>(glot ? glot + cover : nullptr, n - cover, s)) != PVX_OK ||
+        (rc = zero_out<DEV>(dglot ? dglot + cover : nullptr, n - cover, s)) != PVX_OK) return rc;
+    if (DEV) PVX_HIP_CHECK(hipStreamSynchronize(s));                  // (before the buffers of this call are freed, too)
+    return nfr;
+}
+
+extern "C" int64_t pvx_iaif(const void* x, int x_dtype, int64_t n, int nwind, int hop, int64_t nfr, const double* hp_b, int ntaps,
+                            const double* lpc_wind, const double* ola_wind, int tract_order, int glottal_order, double leak, int n_it,
+                            double* glot, double* dglot, double* g, double* dg, double* vt, double* gc, int64_t* singular_frame) {
+    return iaif_body<false>(x, x_dtype, n, nwind, hop, nfr, hp_b, ntaps, lpc_wind, ola_wind, tract_order, glottal_order, leak, n_it, glot, dglot,
+                            g, dg, vt, gc, singular_frame, nullptr);
+}
+
+extern "C" int64_t pvx_iaif_dev(const void* d_x, int x_dtype, int64_t n, int nwind, int hop, int64_t nfr, const double* hp_b, int ntaps,
+                                const double* lpc_wind, const double* ola_wind, int tract_order, int glottal_order, double leak, int n_it,
+                                double* d_glot, double* d_dglot, double* d_g, double* d_dg, double* d_vt, double* d_gc,
+                                int64_t* singular_frame, void* stream) {
+    return iaif_body<true>(d_x, x_dtype, n, nwind, hop, nfr, hp_b, ntaps, lpc_wind, ola_wind, tract_order, glottal_order, leak, n_it, d_glot,
+                           d_dglot, d_g, d_dg, d_vt, d_gc, singular_frame, (hipStream_t)stream);
+}
+
+template <bool DEV>
+static int64_t lpc_body(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int order, double* coef,
+                        int64_t* singular_frame, hipStream_t s) {
+    if (singular_frame) *singular_frame = -1;
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_iaif_kernels = "";
+    if ((rc = lpc_frames_args("pvx_lpc", x_dtype, n, nwind, hop, nfr)) != PVX_OK) return rc;
+    if (order < 0) { pvx_set_error("bad pvx_lpc argument"); return PVX_ERR_INVALID; }
+    if (nwind > PVX_LPC_MAX_NWIND || order > PVX_LPC_MAX_ORDER) {
+        pvx_set_error("pvx_lpc: nwind %d, order %d: the kernel takes nwind <= %d and orders <= %d", nwind, order, PVX_LPC_MAX_NWIND, PVX_LPC_MAX_ORDER);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    if (nfr == 0) return 0;
+    if (!x || !coef) { pvx_set_error("null pvx_lpc signal or output"); return PVX_ERR_INVALID; }
+    const size_t es = dtype_size(x_dtype), limit = iaif_limit(), rb = (size_t)(order + 1) * 8;
+    int64_t fc = nfr;
+    DevMem dx, dc;
+    if (!DEV) {                                                       // whole frames per chunk; the device form reads and writes in place
+        fc = (int64_t)(limit / es) > nwind ? ((int64_t)(limit / es) - nwind) / hop + 1 : 1;
+        fc = std::min(nfr, std::min<int64_t>(fc, std::max<int64_t>(1, (int64_t)(limit / rb))));
+        if ((rc = dx.alloc((size_t)((fc - 1) * hop + nwind) * es)) != PVX_OK || (rc = dc.alloc((size_t)fc * rb)) != PVX_OK) return rc;
+    }
+    for (int64_t f0 = 0; f0 < nfr; f0 += fc) {
+        const int64_t cnt = std::min(fc, nfr - f0);
+        const void* cx = (const char*)x + (size_t)(f0 * hop) * es;
+        if (!DEV) {
+            if ((rc = host_to_device(dx.get(), cx, (size_t)((cnt - 1) * hop + nwind) * es)) != PVX_OK) return rc;
+            cx = dx.get();
+        }
+        int64_t sing = -1;
+        if ((rc = pvx_lpc_run(cx, x_dtype, cnt, wind, nwind, hop, order, DEV ? coef + (size_t)f0 * (order + 1) : dc.as<double>(), &sing, s,
+                              &t_iaif_kernels)) != PVX_OK) return rc;   // synchronises the stream
+        if (sing >= 0) {
+            if (singular_frame) *singular_frame = f0 + sing;
+            pvx_set_error("pvx_lpc: frame %lld: Singular principal minor (a prediction error of exactly 0)", (long long)(f0 + sing));
+            return PVX_ERR_SINGULAR;
+        }
+        if (!DEV && (rc = device_to_host((char*)coef + (size_t)f0 * rb, dc.get(), (size_t)cnt * rb)) != PVX_OK) return rc;
+    }
+    return nfr;
+}
+
+extern "C" int64_t pvx_lpc(const void* x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int order, double* coef,
+                           int64_t* singular_frame) {
+    return lpc_body<false>(x, x_dtype, n, wind, nwind, hop, nfr, order, coef, singular_frame, nullptr);
+}
+
+extern "C" int64_t pvx_lpc_dev(const void* d_x, int x_dtype, int64_t n, const double* wind, int nwind, int hop, int64_t nfr, int order,
+                               double* d_coef, int64_t* singular_frame, void* stream) {
+    return lpc_body<true>(d_x, x_dtype, n, wind, nwind, hop, nfr, order, d_coef, singular_frame, (hipStream_t)stream);
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

@@ -349,6 +349,23 @@ int pvx_specdesc_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_
 int pvx_xspec_run(const void* d_x, const void* d_y, int x_dtype, const double* h_wind, int nwind, int step, int64_t delta, int64_t nblk,
                   int nseg, double* d_sxy, double* d_sxx, double* d_syy, hipStream_t s, const char** kernels);
 
+// glottal inverse filtering and frame-wise LPC (k_iaif.hip; include/pvx.h: pvx_iaif, pvx_lpc).  The tables are host arrays.
+struct IaifCall {
+    int x_dtype, nwind, hop, ntaps, pt, pg, n_it;
+    double leak;
+    const double *h_b, *h_hw, *h_ow;   // [ntaps], [nwind], [nwind] (h_ow: only with an overlap-add)
+};
+// Frames f0 .. f0 + nf - 1 of a signal, d_x pointing at the first sample of frame f0: g, dg into rows 0 .. nf - 1 of d_g / d_dg
+// [nf][nwind], the filters into d_vt [nf][pt + 1] and d_gc [nf][(n_it ? pg : 1) + 1] (all four required, device memory).  With
+// d_glot or d_dglot: the overlap-add of the signal's samples s0 .. s0 + ns - 1 into their elements 0 .. ns - 1, from these rows
+// (which must hold every frame that covers one of the samples).  *singular: the first row whose LPC was singular, or -1.
+// Synchronises the stream.
+int pvx_iaif_run(const IaifCall& c, const void* d_x, int64_t f0, int64_t nf, double* d_g, double* d_dg, double* d_vt, double* d_gc, int64_t s0,
+                 int64_t ns, double* d_glot, double* d_dglot, int64_t* singular, hipStream_t s, const char** kernels);
+// coefficient rows of nf frames (frame i at d_x[i * hop]); h_wind may be null.  Synchronises the stream.
+int pvx_lpc_run(const void* d_x, int x_dtype, int64_t nf, const double* h_wind, int nwind, int hop, int order, double* d_coef, int64_t* singular,
+                hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)
