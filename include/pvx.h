@@ -38,7 +38,8 @@ typedef enum {
     PVX_ERR_ALLOC = -4,       /* device or host allocation failed */
     PVX_ERR_UNSUPPORTED = -5, /* valid request outside what the kernels handle */
     PVX_ERR_SIZE = -6,        /* caller buffer too small / wrong length */
-    PVX_ERR_SINGULAR = -7     /* a frame's Toeplitz system has a zero prediction error (pvx_lpc, pvx_iaif) */
+    PVX_ERR_SINGULAR = -7,    /* a frame's Toeplitz system has a zero prediction error (pvx_lpc, pvx_iaif) */
+    PVX_ERR_NOCONV = -8       /* a polynomial's root iteration met its bound of iterations (pvx_polyroots, pvx_formants) */
 } pvx_status;
 
 /* sample types accepted for the input signal x (PV.py:84 copies whatever the caller passed) */
@@ -570,6 +571,50 @@ int64_t pvx_iaif_dev(const void* d_x, int x_dtype, int64_t n, int nwind, int hop
                      double* d_glot, double* d_dglot, double* d_g, double* d_dg, double* d_vt, double* d_gc,
                      int64_t* singular_frame, void* stream);
 const char* pvx_iaif_last_kernels(void);
+
+/* ---- formants and polynomial roots (pypevoc/speech/SpeechAnalysis.py: Formants :220-319, lpc2form :186-209;
+ *      pypevoc/speech/glottal.py: lpcc2pole :249-272; FORMANTS.md) ----
+ *
+ * pvx_polyroots: the roots of n real polynomials coef[i][0] z^order + ... + coef[i][order] (np.roots' argument order), one
+ * wave per polynomial.  1 <= order <= PVX_ROOTS_MAX_ORDER, else PVX_ERR_UNSUPPORTED and no launch; a zero leading coefficient
+ * is PVX_ERR_INVALID.  re, im [n][order], canonical: a real root has imaginary part +0.0 and complex roots are exact conjugate
+ * pairs, trailing coefficients that are exactly 0 give exact zero roots.  Order within a row: first the nkept[i] roots with
+ * imag >= 0 by ascending atan2(im, re), equal angles by ascending |z|, then their conjugates in the partners' order.
+ * status [n]: 0, or 2 where the iteration met its compile-time bound of iterations without converging; the call then returns
+ * PVX_ERR_NOCONV with the first such row in *noconv_row (nullable; -1 otherwise).  re, im, nkept, status are each nullable.
+ *
+ * pvx_formants: Formants' device half.  d[i] = x[i] - x[i+1] with the last sample unchanged (preemph != 0; else d = x), samples
+ * widened to float64 first; y = resample_poly(d, 1, down): y[m] = sum_k taps[ntaps-1-k] dz[m down + k - (ntaps-1)/2] over the
+ * zero extension dz of d, m < ceil(n / down), the taps in ascending k (down == 1: y = d, taps unused and nullable; else ntaps
+ * is odd); the frames y[i*hop : i*hop+nwind] * wind, i < nfr, go through pvx_lpc's autocorrelation and Levinson recursion at
+ * `order` and the roots of [1, a_1 .. a_order] through pvx_polyroots' iteration.  Rows per frame, each nullable:
+ *   nkept            the number of roots with imag >= 0
+ *   freq, bw [order] atan2(im, re) fs / 2 pi and -0.5 (fs / 2 pi) log |z| of those roots in the order above, NaN beyond nkept
+ *   re, im   [order] all roots, canonical and ordered as pvx_polyroots'
+ *   lpc    [order+1] [1, a_1 .. a_order]
+ * The last decimated sample read, (nfr-1)*hop + nwind - 1, must lie inside ceil(n / down), else PVX_ERR_SIZE.  Limits:
+ * 1 <= nwind <= PVX_LPC_MAX_NWIND, 1 <= order <= PVX_ROOTS_MAX_ORDER; beyond them PVX_ERR_UNSUPPORTED and no launch.  A
+ * silent frame returns PVX_ERR_SINGULAR and *singular_frame as pvx_lpc does, a frame whose roots did not converge
+ * PVX_ERR_NOCONV and *noconv_row.  All arithmetic is float64 with every sum in a fixed order.  Frames are processed in groups
+ * sized by PVX_MAX_DEVICE_BYTES (per buffer), a group decimating only the samples its frames read: the bits do not depend on
+ * the grouping or on where the samples came from.  The _dev forms take device memory for x (coef) and every output (taps and
+ * wind stay host arrays), work on `stream` and are synchronised before they return.  All four return nfr / n or a negative
+ * status.  pvx_formants_last_kernels: what the calling thread's last call of the four ran ("k_preemph_decim+k_formant_frames",
+ * "k_polyroots"; "" when it launched nothing).
+ */
+#define PVX_ROOTS_MAX_ORDER 64
+int64_t pvx_polyroots(const double* coef, int64_t n, int order, double* re, double* im, int32_t* nkept, int32_t* status,
+                      int64_t* noconv_row);
+int64_t pvx_polyroots_dev(const double* d_coef, int64_t n, int order, double* d_re, double* d_im, int32_t* d_nkept, int32_t* d_status,
+                          int64_t* noconv_row, void* stream);
+int64_t pvx_formants(const void* x, int x_dtype, int64_t n, int preemph, int down, const double* taps, int ntaps, const double* wind,
+                     int nwind, int hop, int64_t nfr, int order, double fs, int32_t* nkept, double* freq, double* bw, double* re,
+                     double* im, double* lpc, int64_t* singular_frame, int64_t* noconv_row);
+int64_t pvx_formants_dev(const void* d_x, int x_dtype, int64_t n, int preemph, int down, const double* taps, int ntaps,
+                         const double* wind, int nwind, int hop, int64_t nfr, int order, double fs, int32_t* d_nkept, double* d_freq,
+                         double* d_bw, double* d_re, double* d_im, double* d_lpc, int64_t* singular_frame, int64_t* noconv_row,
+                         void* stream);
+const char* pvx_formants_last_kernels(void);
 
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *

@@ -16,6 +16,7 @@ PVX_SYNTH_F32 = 2
 PVX_ERR_SIZE = -6            # include/pvx.h
 PVX_ERR_UNSUPPORTED = -5
 PVX_ERR_SINGULAR = -7
+PVX_ERR_NOCONV = -8
 PVX_F32, PVX_F64, PVX_I16 = 0, 1, 2
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -160,6 +161,15 @@ SIGNATURES = {
                                       ctypes.c_int, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int] +
                      [ctypes.c_void_p] * 6 + [c_int64_p, ctypes.c_void_p]),
     "pvx_iaif_last_kernels": (ctypes.c_char_p, []),
+    "pvx_polyroots": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int64_p]),
+    "pvx_polyroots_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4 + [c_int64_p, ctypes.c_void_p]),
+    "pvx_formants": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
+                                      c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double, c_int32_p] +
+                     [c_double_p] * 5 + [c_int64_p, c_int64_p]),
+    "pvx_formants_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
+                                          c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double] +
+                         [ctypes.c_void_p] * 6 + [c_int64_p, c_int64_p, ctypes.c_void_p]),
+    "pvx_formants_last_kernels": (ctypes.c_char_p, []),
 }
 
 

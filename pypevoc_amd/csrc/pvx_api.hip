@@ -2635,6 +2635,176 @@ extern "C" int64_t pvx_lpc_dev(const void* d_x, int x_dtype, int64_t n, const do
     return lpc_body<true>(d_x, x_dtype, n, wind, nwind, hop, nfr, order, d_coef, singular_frame, (hipStream_t)stream);
 }
 
+// ---- formants and polynomial roots (k_formant.hip) -------------------------------
+static thread_local const char* t_formants_kernels = "";
+extern "C" const char* pvx_formants_last_kernels(void) { return t_formants_kernels; }
+
+// Frames in groups sized by PVX_MAX_DEVICE_BYTES (per buffer, as iaif_body): a group decimates the samples its own frames read
+// and nothing else.  A decimated sample's value depends on its index and the signal alone, a frame's on its samples alone: the
+// bits are those of one group.
+template <bool DEV>
+static int64_t formants_body(const void* x, int x_dtype, int64_t n, int preemph, int down, const double* taps, int ntaps, const double* wind,
+                             int nwind, int hop, int64_t nfr, int order, double fs, int32_t* nkept, double* freq, double* bw, double* re,
+                             double* im, double* lpc, int64_t* singular_frame, int64_t* noconv_row, hipStream_t s) {
+    if (singular_frame) *singular_frame = -1;
+    if (noconv_row) *noconv_row = -1;
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_formants_kernels = "";
+    if (down < 1 || n < 0 || n > INT64_MAX - down) { pvx_set_error("bad pvx_formants argument"); return PVX_ERR_INVALID; }
+    const int64_t nd = (n + down - 1) / down;                         // the decimated signal: ceil(n / down) samples
+    if ((rc = lpc_frames_args("pvx_formants", x_dtype, nd, nwind, hop, nfr)) != PVX_OK) return rc;
+    if (!wind || order < 1 || (down > 1 && (!taps || ntaps < 1 || ntaps % 2 == 0))) {
+        pvx_set_error("bad pvx_formants argument (order >= 1, a window, and an odd number of taps at down > 1)");
+        return PVX_ERR_INVALID;
+    }
+    if (nwind > PVX_LPC_MAX_NWIND || order > PVX_ROOTS_MAX_ORDER) {
+        pvx_set_error("pvx_formants: nwind %d, order %d: the kernel takes nwind <= %d and orders <= %d", nwind, order, PVX_LPC_MAX_NWIND,
+                      PVX_ROOTS_MAX_ORDER);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    if (nfr == 0) return 0;
+    if (!x) { pvx_set_error("null pvx_formants signal"); return PVX_ERR_INVALID; }
+    const size_t es = dtype_size(x_dtype), limit = iaif_limit();
+    const int nt = down > 1 ? ntaps : 1, half = (nt - 1) / 2;
+    // samples a group of k frames reads: ((k - 1) hop + nwind - 1) down + nt + 1 (the last one for the difference)
+    const int64_t span1 = (int64_t)(nwind - 1) * down + nt + 1, step = (int64_t)hop * down;
+    int64_t cap = (int64_t)(limit / 8) > nwind ? ((int64_t)(limit / 8) - nwind) / hop + 1 : 1;
+    cap = std::min<int64_t>(cap, (int64_t)(limit / es) > span1 ? ((int64_t)(limit / es) - span1) / step + 1 : 1);
+    const int64_t own = std::min(nfr, std::max<int64_t>(1, cap));
+    const size_t P = (size_t)order;
+    DevMem dx, dy, wk, wf, wb, wr, wi, wl;
+    if ((rc = dy.alloc((size_t)((own - 1) * hop + nwind) * 8)) != PVX_OK) return rc;
+    if (!DEV) {
+        if ((rc = dx.alloc((size_t)std::min<int64_t>(n, (own - 1) * step + span1) * es)) != PVX_OK || (rc = wk.alloc((size_t)own * 4)) != PVX_OK ||
+            (rc = wf.alloc((size_t)own * P * 8)) != PVX_OK || (rc = wb.alloc((size_t)own * P * 8)) != PVX_OK ||
+            (rc = wr.alloc((size_t)own * P * 8)) != PVX_OK || (rc = wi.alloc((size_t)own * P * 8)) != PVX_OK ||
+            (rc = wl.alloc((size_t)own * (P + 1) * 8)) != PVX_OK) return rc;
+    }
+    const FormantCall call = {x_dtype, n, preemph != 0, down, nt, nwind, hop, order, fs, taps, wind};
+    for (int64_t fa = 0; fa < nfr; fa += own) {
+        const int64_t nf = std::min(own, nfr - fa);
+        const int64_t m0 = fa * hop, m1 = m0 + (nf - 1) * hop + nwind;
+        const int64_t lo = std::max<int64_t>(0, m0 * down - half), hi = std::min<int64_t>(n, (m1 - 1) * down - half + nt + 1);
+        const void* cx = x;
+        int64_t x0 = 0;
+        if (!DEV) {
+            if ((rc = host_to_device(dx.get(), (const char*)x + (size_t)lo * es, (size_t)(hi - lo) * es)) != PVX_OK) return rc;
+            cx = dx.get();
+            x0 = lo;
+        }
+        const size_t r0 = (size_t)fa;
+        const FormantRows rows = DEV ? FormantRows{nkept ? nkept + r0 : nullptr, freq ? freq + r0 * P : nullptr, bw ? bw + r0 * P : nullptr,
+                                                   re ? re + r0 * P : nullptr, im ? im + r0 * P : nullptr, lpc ? lpc + r0 * (P + 1) : nullptr}
+                                     : FormantRows{wk.as<int>(), wf.as<double>(), wb.as<double>(), wr.as<double>(), wi.as<double>(), wl.as<double>()};
+        int64_t sing = -1, noc = -1;
+        if ((rc = pvx_formants_run(call, cx, x0, fa, nf, dy.as<double>(), rows, &sing, &noc, s, &t_formants_kernels)) != PVX_OK) return rc;
+        if (sing >= 0) {
+            if (singular_frame) *singular_frame = fa + sing;
+            pvx_set_error("pvx_formants: frame %lld: Singular principal minor (a prediction error of exactly 0)", (long long)(fa + sing));
+            return PVX_ERR_SINGULAR;
+        }
+        if (noc >= 0) {
+            if (noconv_row) *noconv_row = fa + noc;
+            pvx_set_error("pvx_formants: frame %lld: the root iteration met its bound of iterations", (long long)(fa + noc));
+            return PVX_ERR_NOCONV;
+        }
+        if (!DEV) {
+            const size_t k = (size_t)nf;
+            if ((nkept && (rc = device_to_host(nkept + r0, wk.get(), k * 4)) != PVX_OK) ||
+                (freq && (rc = device_to_host(freq + r0 * P, wf.get(), k * P * 8)) != PVX_OK) ||
+                (bw && (rc = device_to_host(bw + r0 * P, wb.get(), k * P * 8)) != PVX_OK) ||
+                (re && (rc = device_to_host(re + r0 * P, wr.get(), k * P * 8)) != PVX_OK) ||
+                (im && (rc = device_to_host(im + r0 * P, wi.get(), k * P * 8)) != PVX_OK) ||
+                (lpc && (rc = device_to_host(lpc + r0 * (P + 1), wl.get(), k * (P + 1) * 8)) != PVX_OK)) return rc;
+        }
+    }
+    return nfr;
+}
+
+extern "C" int64_t pvx_formants(const void* x, int x_dtype, int64_t n, int preemph, int down, const double* taps, int ntaps, const double* wind,
+                                int nwind, int hop, int64_t nfr, int order, double fs, int32_t* nkept, double* freq, double* bw, double* re,
+                                double* im, double* lpc, int64_t* singular_frame, int64_t* noconv_row) {
+    return formants_body<false>(x, x_dtype, n, preemph, down, taps, ntaps, wind, nwind, hop, nfr, order, fs, nkept, freq, bw, re, im, lpc,
+                                singular_frame, noconv_row, nullptr);
+}
+
+extern "C" int64_t pvx_formants_dev(const void* d_x, int x_dtype, int64_t n, int preemph, int down, const double* taps, int ntaps,
+                                    const double* wind, int nwind, int hop, int64_t nfr, int order, double fs, int32_t* d_nkept, double* d_freq,
+                                    double* d_bw, double* d_re, double* d_im, double* d_lpc, int64_t* singular_frame, int64_t* noconv_row,
+                                    void* stream) {
+    return formants_body<true>(d_x, x_dtype, n, preemph, down, taps, ntaps, wind, nwind, hop, nfr, order, fs, d_nkept, d_freq, d_bw, d_re, d_im,
+                               d_lpc, singular_frame, noconv_row, (hipStream_t)stream);
+}
+
+template <bool DEV>
+static int64_t polyroots_body(const double* coef, int64_t n, int order, double* re, double* im, int32_t* nkept, int32_t* status,
+                              int64_t* noconv_row, hipStream_t s) {
+    if (noconv_row) *noconv_row = -1;
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_formants_kernels = "";
+    if (n < 0 || order < 1) { pvx_set_error("bad pvx_polyroots argument"); return PVX_ERR_INVALID; }
+    if (order > PVX_ROOTS_MAX_ORDER) {
+        pvx_set_error("pvx_polyroots: degree %d: the kernel takes degrees <= %d", order, PVX_ROOTS_MAX_ORDER);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    if (n == 0) return 0;
+    if (!coef) { pvx_set_error("null pvx_polyroots coefficients"); return PVX_ERR_INVALID; }
+    const size_t P = (size_t)order, rb = (P + 1) * 8;
+    if (!DEV)
+        for (int64_t i = 0; i < n; i++)
+            if (coef[(size_t)i * (P + 1)] == 0.0) { pvx_set_error("pvx_polyroots: row %lld has a zero leading coefficient", (long long)i); return PVX_ERR_INVALID; }
+    int64_t rc_rows = n;
+    DevMem dc, wr, wi, wk, wst;
+    if (!DEV) {
+        rc_rows = std::min(n, std::max<int64_t>(1, (int64_t)(iaif_limit() / rb)));
+        if ((rc = dc.alloc((size_t)rc_rows * rb)) != PVX_OK || (rc = wr.alloc((size_t)rc_rows * P * 8)) != PVX_OK ||
+            (rc = wi.alloc((size_t)rc_rows * P * 8)) != PVX_OK || (rc = wk.alloc((size_t)rc_rows * 4)) != PVX_OK ||
+            (rc = wst.alloc((size_t)rc_rows * 4)) != PVX_OK) return rc;
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += rc_rows) {
+        const int64_t cnt = std::min(rc_rows, n - r0);
+        const size_t o = (size_t)r0, k = (size_t)cnt;
+        int64_t noc = -1, lead = -1;
+        if (!DEV) {
+            if ((rc = host_to_device(dc.get(), coef + o * (P + 1), k * rb)) != PVX_OK) return rc;
+            rc = pvx_polyroots_run(dc.as<double>(), cnt, order, wr.as<double>(), wi.as<double>(), wk.as<int>(), wst.as<int>(), &noc, &lead, s,
+                                   &t_formants_kernels);
+        } else {
+            rc = pvx_polyroots_run(coef + o * (P + 1), cnt, order, re ? re + o * P : nullptr, im ? im + o * P : nullptr, nkept ? nkept + o : nullptr,
+                                   status ? status + o : nullptr, &noc, &lead, s, &t_formants_kernels);
+        }
+        if (rc != PVX_OK) return rc;
+        if (!DEV) {
+            if ((re && (rc = device_to_host(re + o * P, wr.get(), k * P * 8)) != PVX_OK) ||
+                (im && (rc = device_to_host(im + o * P, wi.get(), k * P * 8)) != PVX_OK) ||
+                (nkept && (rc = device_to_host(nkept + o, wk.get(), k * 4)) != PVX_OK) ||
+                (status && (rc = device_to_host(status + o, wst.get(), k * 4)) != PVX_OK)) return rc;
+        }
+        if (lead >= 0) {
+            pvx_set_error("pvx_polyroots: row %lld has a zero leading coefficient", (long long)(r0 + lead));
+            return PVX_ERR_INVALID;
+        }
+        if (noc >= 0) {
+            if (noconv_row) *noconv_row = r0 + noc;
+            pvx_set_error("pvx_polyroots: row %lld: the root iteration met its bound of iterations", (long long)(r0 + noc));
+            return PVX_ERR_NOCONV;
+        }
+    }
+    return n;
+}
+
+extern "C" int64_t pvx_polyroots(const double* coef, int64_t n, int order, double* re, double* im, int32_t* nkept, int32_t* status,
+                                 int64_t* noconv_row) {
+    return polyroots_body<false>(coef, n, order, re, im, nkept, status, noconv_row, nullptr);
+}
+
+extern "C" int64_t pvx_polyroots_dev(const double* d_coef, int64_t n, int order, double* d_re, double* d_im, int32_t* d_nkept, int32_t* d_status,
+                                     int64_t* noconv_row, void* stream) {
+    return polyroots_body<true>(d_coef, n, order, d_re, d_im, d_nkept, d_status, noconv_row, (hipStream_t)stream);
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

@@ -366,6 +366,28 @@ int pvx_iaif_run(const IaifCall& c, const void* d_x, int64_t f0, int64_t nf, dou
 int pvx_lpc_run(const void* d_x, int x_dtype, int64_t nf, const double* h_wind, int nwind, int hop, int order, double* d_coef, int64_t* singular,
                 hipStream_t s, const char** kernels);
 
+// formant tracking and polynomial roots (k_formant.hip; include/pvx.h: pvx_formants, pvx_polyroots).  The tables are host arrays.
+struct FormantCall {
+    int x_dtype;
+    int64_t n;                         // the length of the whole signal (the zero extension begins there)
+    int preemph, down, ntaps, nwind, hop, order;
+    double fs;
+    const double *h_taps, *h_wind;     // [ntaps] (down > 1 only), [nwind]
+};
+struct FormantRows {                   // device rows of the group's first frame on; each nullable
+    int* nkept;
+    double *freq, *bw, *re, *im, *lpc;
+};
+// Frames f0 .. f0 + nf - 1 of the decimated signal: d_x[i - x0] is sample i of the signal and holds every sample those
+// frames' decimated samples read (and one more for the difference); d_y takes the (nf - 1) * hop + nwind decimated samples.
+// *singular / *noconv: the first row (from 0) whose LPC was singular / whose roots met the iteration bound, or -1.
+// Synchronises the stream.
+int pvx_formants_run(const FormantCall& c, const void* d_x, int64_t x0, int64_t f0, int64_t nf, double* d_y, const FormantRows& out,
+                     int64_t* singular, int64_t* noconv, hipStream_t s, const char** kernels);
+// canonical, ordered roots of n coefficient rows [order + 1]; d_re / d_im / d_nkept / d_status nullable.  Synchronises the stream.
+int pvx_polyroots_run(const double* d_coef, int64_t n, int order, double* d_re, double* d_im, int* d_nkept, int* d_status, int64_t* noconv,
+                      int64_t* leadzero, hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)

@@ -9,7 +9,8 @@ Deviations from the reference, which cannot run these two as written under Pytho
   Periodogram  raises TypeError there (np.zeros of a float length, :168); here it has the evident meaning, SpectralMoments'
                own frame count, window and specLen = nwind//2.
   rmsWind      without nhop raises TypeError there (a float hop, :327); here nhop=None means nwind//2.
-lpc, lpc2form, lpc2form_full, Formants, refine_max and FricativeData* are not mirrored and raise NotImplementedError."""
+lpc, lpc2form, lpc2form_full, Formants, refine_max and FricativeData* are not mirrored here and raise NotImplementedError;
+working lpc, lpc2form and Formants are in pypevoc_amd.speech.formants (FORMANTS.md)."""
 import numpy as np
 
 from .. import _lib

@@ -7,7 +7,7 @@ one launch: nothing per frame happens in Python, and there is no CPU fallback.  
 per InverseFilter (a numpy restatement of scipy.signal.firls with unit weights: this package imports no scipy).
 
 lpc_frames is the batched form of lpc the reference does not have.  PaddedFilter, fir_pre_phase and lpcc2pole are not
-mirrored and raise NotImplementedError (INTEGRATION.md)."""
+mirrored here and raise NotImplementedError; a working lpcc2pole is in pypevoc_amd.speech.formants."""
 import ctypes
 import logging
 
