@@ -521,6 +521,43 @@ int64_t pvx_xspec_dev(const void* d_x, const void* d_y, int x_dtype, int64_t n, 
                       void* stream);
 const char* pvx_xspec_last_kernels(void);
 
+/* ---- delay estimation: full cross-correlations and their peaks, block by block (pypevoc/TransferFunctions.py:
+ *      determineDelay :80-109, block_delay :188-196, maxdelwind :199-244; DELAY.md) ----
+ *
+ * Block b = 0 .. nblk - 1 reads a[start + b*delta : .. + la] and v[start + b*delta : .. + lv] (la != lv is allowed).  Per block:
+ *   prepare    each of the two on its own: PVX_DETREND_NONE, PVX_DETREND_CONSTANT (the mean is subtracted) or PVX_DETREND_LINEAR
+ *              (the least-squares line is: the mean, then the slope against the centred index, closed form -- scipy.signal.detrend's
+ *              default); then the product with win_a [la] / win_v [lv] (host arrays; null: ones)
+ *   correlate  c[k] = sum_m a'[m + k - (lv-1)] v'[m], k = 0 .. la + lv - 2: numpy's correlate(a', v', "full")
+ *   peak       lag[b] = the k of the largest c[k] (use_abs != 0: of the largest |c[k]|), the lowest k of an exact tie (np.argmax);
+ *              peak[b] = c[lag[b]], signed.  A block of which a' or v' is all zero gives lag 0 and peak +0.0
+ *   corr       nullable: [nblk][la + lv - 1], every c[k]
+ * a, v: float32, float64 or int16 samples (pvx_dtype, one type for both), widened on load; all arithmetic float64, every sum in a
+ * fixed order: a block's values do not depend on the grid, on the other blocks of the call, on how the call was cut into batches
+ * or chunks, or on where the samples came from.  Two routes, chosen once per call: max(la, lv) <= PVX_XCORR_DIRECT_MAX runs
+ * k_xcorr_direct, one workgroup per block with both prepared blocks in LDS and a lag per lane (no rocFFT, no plan); anything
+ * longer, and every length with PVX_XCORR_FFT in the environment, pads both to P, the smallest power of two >= la + lv - 1:
+ * k_xcorr_prep, two batched real rocFFTs, k_xcorr_mul, one inverse real rocFFT, k_xcorr_peak (which scales by 1/P).  P beyond
+ * PVX_XCORR_MAX_P: PVX_ERR_UNSUPPORTED and no launch.  The last sample of the last block must lie inside na samples of a and nv
+ * of v, else PVX_ERR_SIZE; la < 1, lv < 1, delta < 0, start < 0 or an unknown detrend code: PVX_ERR_INVALID.  nblk = 0: nothing
+ * is launched, the outputs are untouched.  Host input is chunked by PVX_MAX_DEVICE_BYTES in whole blocks (at least one), both
+ * signals cut at the same samples.  pvx_xcorr_peak_dev: a, v, lag, peak and corr are device memory (the windows stay host
+ * arrays), work on `stream`, synchronised before the return.  Both return nblk or a negative status; calls share a per-device
+ * workspace kept for the process (grow-only, one pair of rocFFT plans per P in use) and take turns on it.
+ * pvx_xcorr_last_kernels: what the calling thread's last call ran ("k_xcorr_direct",
+ * "k_xcorr_prep+rocfft+k_xcorr_mul+rocfft+k_xcorr_peak"; "" when it had no block).
+ */
+#define PVX_XCORR_DIRECT_MAX 2048
+#define PVX_XCORR_MAX_P (1 << 20)
+typedef enum { PVX_DETREND_NONE = 0, PVX_DETREND_CONSTANT = 1, PVX_DETREND_LINEAR = 2 } pvx_detrend;
+int64_t pvx_xcorr_peak(const void* a, const void* v, int x_dtype, int64_t na, int64_t nv, int la, int lv, int64_t start, int64_t delta,
+                       int64_t nblk, int detrend, const double* win_a, const double* win_v, int use_abs, int32_t* lag, double* peak,
+                       double* corr);
+int64_t pvx_xcorr_peak_dev(const void* d_a, const void* d_v, int x_dtype, int64_t na, int64_t nv, int la, int lv, int64_t start,
+                           int64_t delta, int64_t nblk, int detrend, const double* win_a, const double* win_v, int use_abs,
+                           int32_t* d_lag, double* d_peak, double* d_corr, void* stream);
+const char* pvx_xcorr_last_kernels(void);
+
 /* ---- linear prediction and glottal inverse filtering (pypevoc/speech/glottal.py: lpc :32-34, iaif_ola :36-84,
  *      InverseFilter.apply :190-234; pypevoc/speech/SpeechAnalysis.py: lpc :9-24) ----
  *

@@ -16,9 +16,10 @@ from .FFTFilters import FilterBank, TriangularFilterBank, MelFilterBank, Piecewi
 from . import FFTFilters  # noqa: F401  (`from pypevoc_amd import FFTFilters as ft`, as the reference's examples import it)
 from .Heterodyne import HeterodyneHarmonic, heterodyne  # noqa: F401
 from . import TransferFunctions  # noqa: F401  (`from pypevoc_amd import TransferFunctions`, as `from pypevoc import TransferFunctions`)
+from . import delay  # noqa: F401  (determineDelay, block_delay, maxdelwind: the working forms of TransferFunctions' three stubs)
 from ._lib import PvxError  # noqa: F401
 
 __all__ = ["PV", "PVHarmonic", "SinSum", "RegPartial", "PeakFinder", "PVBatch", "PVMany", "PvxError",
            "PeriodSeries", "PeriodTimeSeries", "period_marks_corr", "period_marks_peak", "period_marks_amdf",
            "FilterBank", "TriangularFilterBank", "MelFilterBank", "PiecewiseFilterSpec", "FFTFilters",
-           "HeterodyneHarmonic", "heterodyne", "TransferFunctions"]
+           "HeterodyneHarmonic", "heterodyne", "TransferFunctions", "delay"]

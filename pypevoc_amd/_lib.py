@@ -18,6 +18,9 @@ PVX_ERR_UNSUPPORTED = -5
 PVX_ERR_SINGULAR = -7
 PVX_ERR_NOCONV = -8
 PVX_F32, PVX_F64, PVX_I16 = 0, 1, 2
+PVX_DETREND_NONE, PVX_DETREND_CONSTANT, PVX_DETREND_LINEAR = 0, 1, 2
+PVX_XCORR_DIRECT_MAX = 2048
+PVX_XCORR_MAX_P = 1 << 20
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -150,6 +153,13 @@ SIGNATURES = {
     "pvx_xspec_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4),
     "pvx_xspec_last_kernels": (ctypes.c_char_p, []),
+    "pvx_xcorr_peak": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int,
+                                        c_int32_p, c_double_p, c_double_p]),
+    "pvx_xcorr_peak_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p,
+                                            ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "pvx_xcorr_last_kernels": (ctypes.c_char_p, []),
     "pvx_lpc": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                  ctypes.c_int, c_double_p, c_int64_p]),
     "pvx_lpc_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,

@@ -2450,6 +2450,89 @@ extern "C" int64_t pvx_xspec(const void* x, const void* y, int x_dtype, int64_t 
     return nblk;
 }
 
+// ---- full cross-correlations and their peaks block by block (k_xcorr.hip) -----------------------
+static thread_local const char* t_xcorr_kernels = "";
+extern "C" const char* pvx_xcorr_last_kernels(void) { return t_xcorr_kernels; }
+
+// samples read: start .. start + (nblk-1)*delta + la - 1 of a, .. + lv - 1 of v
+static int xcorr_args(int x_dtype, int64_t na, int64_t nv, int la, int lv, int64_t start, int64_t delta, int64_t nblk, int detrend,
+                      const int32_t* lag, const double* peak) {
+    if (na < 0 || nv < 0 || la < 1 || lv < 1 || start < 0 || delta < 0 || nblk < 0) { pvx_set_error("bad pvx_xcorr_peak argument"); return PVX_ERR_INVALID; }
+    if (detrend != PVX_DETREND_NONE && detrend != PVX_DETREND_CONSTANT && detrend != PVX_DETREND_LINEAR) {
+        pvx_set_error("pvx_xcorr_peak: unknown detrend code %d", detrend);
+        return PVX_ERR_INVALID;
+    }
+    if (x_dtype != PVX_F32 && x_dtype != PVX_F64 && x_dtype != PVX_I16) { pvx_set_error("bad x_dtype %d", x_dtype); return PVX_ERR_INVALID; }
+    if (nblk > 0) {
+        const __int128 first = (__int128)start + (__int128)(nblk - 1) * delta;
+        if (first + la > (__int128)na || first + lv > (__int128)nv) {
+            pvx_set_error("pvx_xcorr_peak: block %lld (%d and %d samples, blocks %lld apart from %lld) ends beyond the %lld and %lld samples of the signals",
+                          (long long)(nblk - 1), la, lv, (long long)delta, (long long)start, (long long)na, (long long)nv);
+            return PVX_ERR_SIZE;
+        }
+        if (pvx_xcorr_fft_route(la, lv) && ((int64_t)la + lv - 1 > (int64_t)PVX_XCORR_MAX_P || pvx_xcorr_padded(la, lv) == 0)) {
+            pvx_set_error("pvx_xcorr_peak: %d + %d - 1 lags need a transform longer than %d", la, lv, (int)PVX_XCORR_MAX_P);
+            return PVX_ERR_UNSUPPORTED;
+        }
+        if ((__int128)nblk * ((int64_t)la + lv - 1) > ((__int128)1 << 56)) { pvx_set_error("pvx_xcorr_peak: too many blocks"); return PVX_ERR_INVALID; }
+        if (!lag || !peak) { pvx_set_error("null pvx_xcorr_peak output"); return PVX_ERR_INVALID; }
+    }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_xcorr_peak_dev(const void* d_a, const void* d_v, int x_dtype, int64_t na, int64_t nv, int la, int lv, int64_t start,
+                                      int64_t delta, int64_t nblk, int detrend, const double* win_a, const double* win_v, int use_abs,
+                                      int32_t* d_lag, double* d_peak, double* d_corr, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_xcorr_kernels = "";
+    if ((rc = xcorr_args(x_dtype, na, nv, la, lv, start, delta, nblk, detrend, d_lag, d_peak)) != PVX_OK) return rc;
+    if (nblk == 0) return 0;
+    if (!d_a || !d_v) { pvx_set_error("null pvx_xcorr_peak signal"); return PVX_ERR_INVALID; }
+    const size_t es = dtype_size(x_dtype);
+    if ((rc = pvx_xcorr_run((const char*)d_a + (size_t)start * es, (const char*)d_v + (size_t)start * es, x_dtype, la, lv, delta, nblk, detrend, win_a,
+                            win_v, use_abs, d_lag, d_peak, d_corr, (hipStream_t)stream, &t_xcorr_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nblk;
+}
+
+extern "C" int64_t pvx_xcorr_peak(const void* a, const void* v, int x_dtype, int64_t na, int64_t nv, int la, int lv, int64_t start, int64_t delta,
+                                  int64_t nblk, int detrend, const double* win_a, const double* win_v, int use_abs, int32_t* lag, double* peak,
+                                  double* corr) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_xcorr_kernels = "";
+    if ((rc = xcorr_args(x_dtype, na, nv, la, lv, start, delta, nblk, detrend, lag, peak)) != PVX_OK) return rc;
+    if (nblk == 0) return 0;
+    if (!a || !v) { pvx_set_error("null pvx_xcorr_peak signal"); return PVX_ERR_INVALID; }
+    // a chunk is whole blocks with the samples they read, the same cut for both signals: a block's bits are those of the
+    // unchunked call
+    size_t limit = (size_t)2 << 30;                                   // per buffer
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long x = atoll(e); if (x > 0) limit = (size_t)x; }
+    const size_t es = dtype_size(x_dtype);
+    const int64_t nlag = (int64_t)la + lv - 1;
+    const int64_t span = std::max(la, lv);                            // samples of the longer block
+    const int64_t room = (int64_t)(limit / es);
+    int64_t bc = nblk;
+    if (delta > 0) bc = std::min<int64_t>(bc, room > span ? (room - span) / delta + 1 : 1);
+    bc = std::min<int64_t>(bc, std::max<int64_t>(1, (int64_t)(limit / ((size_t)(corr ? nlag : 1) * 8))));
+    DevMem da, dv, dlag, dpeak, dcorr;
+    if ((rc = da.alloc((size_t)((bc - 1) * delta + la) * es)) != PVX_OK || (rc = dv.alloc((size_t)((bc - 1) * delta + lv) * es)) != PVX_OK ||
+        (rc = dlag.alloc((size_t)bc * 4)) != PVX_OK || (rc = dpeak.alloc((size_t)bc * 8)) != PVX_OK ||
+        (corr && (rc = dcorr.alloc((size_t)(bc * nlag) * 8)) != PVX_OK)) return rc;
+    for (int64_t b0 = 0; b0 < nblk; b0 += bc) {
+        const int64_t cnt = std::min(bc, nblk - b0);
+        const size_t off = (size_t)(start + b0 * delta) * es;
+        if ((rc = host_to_device(da.get(), (const char*)a + off, (size_t)((cnt - 1) * delta + la) * es)) != PVX_OK ||
+            (rc = host_to_device(dv.get(), (const char*)v + off, (size_t)((cnt - 1) * delta + lv) * es)) != PVX_OK) return rc;
+        if ((rc = pvx_xcorr_run(da.get(), dv.get(), x_dtype, la, lv, delta, cnt, detrend, win_a, win_v, use_abs, dlag.as<int32_t>(), dpeak.as<double>(),
+                                corr ? dcorr.as<double>() : nullptr, nullptr, &t_xcorr_kernels)) != PVX_OK) return rc;
+        if ((rc = device_to_host((char*)lag + (size_t)b0 * 4, dlag.get(), (size_t)cnt * 4)) != PVX_OK ||
+            (rc = device_to_host((char*)peak + (size_t)b0 * 8, dpeak.get(), (size_t)cnt * 8)) != PVX_OK) return rc;
+        if (corr && (rc = device_to_host((char*)corr + (size_t)(b0 * nlag) * 8, dcorr.get(), (size_t)(cnt * nlag) * 8)) != PVX_OK) return rc;
+    }
+    return nblk;
+}
+
 // ---- linear prediction and glottal inverse filtering (k_iaif.hip) -------------------------------
 static thread_local const char* t_iaif_kernels = "";
 extern "C" const char* pvx_iaif_last_kernels(void) { return t_iaif_kernels; }

@@ -349,6 +349,16 @@ int pvx_specdesc_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_
 int pvx_xspec_run(const void* d_x, const void* d_y, int x_dtype, const double* h_wind, int nwind, int step, int64_t delta, int64_t nblk,
                   int nseg, double* d_sxy, double* d_sxx, double* d_syy, hipStream_t s, const char** kernels);
 
+// full cross-correlations and their peaks, block by block (k_xcorr.hip; include/pvx.h: pvx_xcorr_peak): nblk blocks of the device
+// signals d_a (la samples a block) and d_v (lv), which point at the first block's first sample.  The windows are host arrays
+// (nullable: ones), the outputs device memory (d_corr [nblk][la + lv - 1], nullable).  Synchronises the stream.
+// pvx_xcorr_fft_route: whether a call of these lengths takes the fft route; pvx_xcorr_padded: its padded length P, 0 beyond
+// PVX_XCORR_MAX_P (la, lv >= 1)
+bool pvx_xcorr_fft_route(int la, int lv);
+int pvx_xcorr_padded(int la, int lv);
+int pvx_xcorr_run(const void* d_a, const void* d_v, int x_dtype, int la, int lv, int64_t delta, int64_t nblk, int detrend, const double* h_win_a,
+                  const double* h_win_v, int use_abs, int32_t* d_lag, double* d_peak, double* d_corr, hipStream_t s, const char** kernels);
+
 // glottal inverse filtering and frame-wise LPC (k_iaif.hip; include/pvx.h: pvx_iaif, pvx_lpc).  The tables are host arrays.
 struct IaifCall {
     int x_dtype, nwind, hop, ntaps, pt, pg, n_it;

@@ -1,5 +1,5 @@
 // pvx_mem.h -- host only: move-only owners of what the host layer allocates (device and page-locked memory, events, streams,
-// a real-forward rocFFT plan).  A destructor releases what its object holds; a failed step leaves the object empty.
+// a real rocFFT plan, forward or inverse).  A destructor releases what its object holds; a failed step leaves the object empty.
 //
 // Workspaces that live as long as the process (PeriodWs, FbankWs, the plan-less tracker's and the process-wide staging
 // rings; k_synth.hip's per-stream map holds raw pointers) are heap objects that are never deleted: they may have these owners
@@ -86,8 +86,9 @@ public:
 using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
 
-// A batched 1-D real -> Hermitian-interleaved rocFFT plan with its execution info.  `work` is the plan's own work buffer, for
-// the callers that do not share one between plans or keep it beyond a plan; either kind reaches the plan through set_work().
+// A batched 1-D real -> Hermitian-interleaved rocFFT plan (create), or its inverse (create_inverse), with its execution info.
+// `work` is the plan's own work buffer, for the callers that do not share one between plans or keep it beyond a plan; either
+// kind reaches the plan through set_work().
 class RealFft {
     rocfft_plan plan_ = nullptr;
     rocfft_execution_info info_ = nullptr;
@@ -119,20 +120,34 @@ public:
     // `batch` transforms of `len` reals, idist reals / odist complex values apart; on failure the object is empty and *st says why
     Step create(size_t len, size_t batch, rocfft_precision precision, rocfft_result_placement placement, size_t idist, size_t odist,
                 rocfft_status* st) {
+        return make(false, len, batch, precision, placement, idist, odist, st);
+    }
+    // the inverse sibling: `batch` Hermitian-interleaved half spectra of len/2 + 1 complex values, idist complex values apart, to
+    // `len` reals each, odist reals apart, unscaled (the caller divides by len).  rocFFT may overwrite the spectra it reads
+    Step create_inverse(size_t len, size_t batch, rocfft_precision precision, rocfft_result_placement placement, size_t idist,
+                        size_t odist, rocfft_status* st) {
+        return make(true, len, batch, precision, placement, idist, odist, st);
+    }
+private:
+    Step make(bool inverse, size_t len, size_t batch, rocfft_precision precision, rocfft_result_placement placement, size_t idist,
+              size_t odist, rocfft_status* st) {
         reset();
         rocfft_plan_description desc = nullptr;
         if ((*st = rocfft_plan_description_create(&desc)) != rocfft_status_success) return describe;
         size_t istride = 1, ostride = 1;
-        *st = rocfft_plan_description_set_data_layout(desc, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, nullptr, nullptr,
-                                                      1, &istride, idist, 1, &ostride, odist);
+        *st = rocfft_plan_description_set_data_layout(desc, inverse ? rocfft_array_type_hermitian_interleaved : rocfft_array_type_real,
+                                                      inverse ? rocfft_array_type_real : rocfft_array_type_hermitian_interleaved, nullptr,
+                                                      nullptr, 1, &istride, idist, 1, &ostride, odist);
         if (*st == rocfft_status_success)
-            *st = rocfft_plan_create(&plan_, placement, rocfft_transform_type_real_forward, precision, 1, &len, batch, desc);
+            *st = rocfft_plan_create(&plan_, placement, inverse ? rocfft_transform_type_real_inverse : rocfft_transform_type_real_forward,
+                                     precision, 1, &len, batch, desc);
         (void)rocfft_plan_description_destroy(desc);
         if (*st != rocfft_status_success) { plan_ = nullptr; return plan; }
         if ((*st = rocfft_plan_get_work_buffer_size(plan_, &work_bytes_)) == rocfft_status_success) *st = rocfft_execution_info_create(&info_);
         if (*st != rocfft_status_success) { info_ = nullptr; reset(); return info; }
         return done;
     }
+public:
     rocfft_status set_work(void* buf, size_t bytes) { return rocfft_execution_info_set_work_buffer(info_, buf, bytes); }
     rocfft_status execute(void* in, void* out, hipStream_t s) {
         const rocfft_status st = rocfft_execution_info_set_stream(info_, s);

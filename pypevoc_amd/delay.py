@@ -1,0 +1,178 @@
+"""Delay estimation on the device: the working forms of determineDelay (pypevoc/TransferFunctions.py:80-109), block_delay
+(:188-196) and maxdelwind (:199-244), whose names in pypevoc_amd.TransferFunctions stay stubs, and the primitive under them,
+xcorr_peaks: the full cross-correlations of the blocks of two signals and their peaks, one call of pvx_xcorr_peak (k_xcorr.hip,
+include/pvx.h; DELAY.md) for all the blocks.  Nothing runs per block in Python.  Neither scipy nor matplotlib is imported.
+
+Signals are host arrays or 1-D float32 / float64 / int16 tensors already on the GPU, read in place.  No CPU fallback.
+Deviations from the reference: integer input gives a float64 strength; non-finite samples are undefined; an
+exactly constant block (exactly a line under the linear detrend) leaves rounding residue here as there, and its arg-max is
+arbitrary in both; exact ties between distinct lags of a non-silent block are not preserved by the FFT route."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .TransferFunctions import block_starts
+
+_DETREND = {None: _lib.PVX_DETREND_NONE, False: _lib.PVX_DETREND_NONE, "none": _lib.PVX_DETREND_NONE,
+            "constant": _lib.PVX_DETREND_CONSTANT, "linear": _lib.PVX_DETREND_LINEAR}
+
+
+def last_kernels():
+    """The kernels the calling thread's last device call ran: 'k_xcorr_direct' or
+    'k_xcorr_prep+rocfft+k_xcorr_mul+rocfft+k_xcorr_peak' ('' when the call had no block; a maxdelwind without a block makes no
+    device call)."""
+    return _lib.load().pvx_xcorr_last_kernels().decode()
+
+
+def _siglen(x):
+    if _lib.is_device_array(x):
+        s = _lib.DeviceSignal(x)
+        if len(s.shape) != 1:
+            raise ValueError("1-D signals are expected")
+        return s.shape[0]
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError("1-D signals are expected")
+    return len(x)
+
+
+def _window(w, n, what):
+    if w is None:
+        return None
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (n,):
+        raise ValueError("%s must have the %d samples of its block" % (what, n))
+    return w
+
+
+def _signals(a, v):
+    """The two signals as the entry points take them; every complaint about them is made before the device is touched."""
+    if _lib.is_device_array(a) != _lib.is_device_array(v):
+        raise TypeError("both signals must be host arrays, or both device-resident")
+    if _lib.is_device_array(a):
+        sa, sv = _lib.DeviceSignal(a), _lib.DeviceSignal(v)
+        if len(sa.shape) != 1 or len(sv.shape) != 1:
+            raise ValueError("1-D signals are expected")
+        if sa.dtype_code != sv.dtype_code:
+            raise TypeError("device-resident signals must share one sample type (got %s and %s)" % (sa.dtype, sv.dtype))
+        return True, sa, sv, sa.dtype_code
+    if np.iscomplexobj(a) or np.iscomplexobj(v):
+        raise NotImplementedError("complex signals are not mirrored (INTEGRATION.md)")
+    xa, code = _lib.as_signal(a)
+    xv, codev = _lib.as_signal(v)
+    if xa.ndim != 1 or xv.ndim != 1:
+        raise ValueError("1-D signals are expected")
+    if codev != code:                                                # one sample type for both: the wider one holds either exactly
+        xa, xv, code = np.ascontiguousarray(xa, dtype=np.float64), np.ascontiguousarray(xv, dtype=np.float64), _lib.PVX_F64
+    return False, xa, xv, code
+
+
+def xcorr_peaks(a, v, la, lv=None, start=0, delta=None, nblk=None, window_a=None, window_v=None, detrend="none", use_abs=False,
+                full=False):
+    """(lag, peak) -- with full=True (lag, peak, corr) -- of the blocks b = 0 .. nblk - 1, a[start + b*delta : .. + la] against
+    v[start + b*delta : .. + lv] (lv=None: la; delta=None: la; nblk=None: as many as lie inside both signals).  Per block, each
+    of the two is detrended on its own ('none', 'constant': the mean, 'linear': the least-squares line), multiplied by its
+    window (la / lv values; None: ones) and correlated: corr[b] = np.correlate(a', v', 'full'), float64 [la + lv - 1];
+    lag[b] (int64) = np.argmax(corr[b]), or of abs(corr[b]) with use_abs; peak[b] = corr[b][lag[b]], signed.
+    A block of which either prepared half is all zero gives lag 0 and peak 0.0.  Raises PvxError without a GPU."""
+    la = int(la)
+    lv = la if lv is None else int(lv)
+    start = int(start)
+    delta = la if delta is None else int(delta)
+    if detrend not in _DETREND:
+        raise ValueError("detrend must be 'none', 'constant' or 'linear'")
+    if la < 1 or lv < 1 or start < 0 or delta < 0:
+        raise ValueError("block lengths of at least one sample, a start and a distance between blocks that are not negative are expected")
+    on_device, sa, sv, code = _signals(a, v)
+    na, nv = (sa.shape[0], sv.shape[0]) if on_device else (len(sa), len(sv))
+    if nblk is None:
+        room = min(na - la, nv - lv) - start
+        nblk = 0 if room < 0 else (room // delta + 1 if delta > 0 else 1)
+    nblk = max(int(nblk), 0)
+    wa, wv = _window(window_a, la, "window_a"), _window(window_v, lv, "window_v")
+    nlag = la + lv - 1
+    lib = _lib.load()
+    bound = _lib.init()
+    mode = _DETREND[detrend]
+    pa = None if wa is None else _lib.dptr(wa)
+    pv = None if wv is None else _lib.dptr(wv)
+    if on_device:
+        import torch
+        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
+            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
+                                % (torch.cuda.current_device(), bound))
+        dev = torch.device("cuda", bound)
+        dlag = torch.empty(max(nblk, 1), dtype=torch.int32, device=dev)
+        dpeak = torch.empty(max(nblk, 1), dtype=torch.float64, device=dev)
+        dcorr = torch.empty(max(nblk * nlag, 1), dtype=torch.float64, device=dev) if full else None
+        stream = torch.cuda.current_stream()
+        got = _lib.check(lib.pvx_xcorr_peak_dev(ctypes.c_void_p(sa.ptr), ctypes.c_void_p(sv.ptr), code, na, nv, la, lv, start, delta, nblk, mode,
+                                                pa, pv, int(bool(use_abs)), ctypes.c_void_p(dlag.data_ptr()), ctypes.c_void_p(dpeak.data_ptr()),
+                                                ctypes.c_void_p(dcorr.data_ptr()) if full else None, ctypes.c_void_p(stream.cuda_stream)),
+                         "pvx_xcorr_peak_dev")
+        lag = dlag.cpu().numpy()[:nblk]
+        peak = dpeak.cpu().numpy()[:nblk]
+        corr = dcorr.cpu().numpy()[:nblk * nlag] if full else None
+    else:
+        lag = np.empty(nblk, dtype=np.int32)
+        peak = np.empty(nblk)
+        corr = np.empty(nblk * nlag) if full else None
+        got = _lib.check(lib.pvx_xcorr_peak(ctypes.c_void_p(sa.ctypes.data), ctypes.c_void_p(sv.ctypes.data), code, na, nv, la, lv, start, delta, nblk,
+                                            mode, pa, pv, int(bool(use_abs)), lag.ctypes.data_as(_lib.c_int32_p), _lib.dptr(peak),
+                                            _lib.dptr(corr) if full else None), "pvx_xcorr_peak")
+    if got != nblk:
+        raise _lib.PvxError("pvx_xcorr_peak returned %d blocks for %d" % (got, nblk))
+    lag = lag.astype(np.int64)
+    return (lag, peak, corr.reshape(nblk, nlag)) if full else (lag, peak)
+
+
+def block_delay(source, target, window=None):
+    """(np.argmax(c) - len(source), np.max(c)) of c = np.correlate(window * source, window * target, 'full') (window None:
+    ones), as the reference computes it: the reference subtracts len(source), not len(source) - 1, so identical signals give -1
+    and an all-zero pair of length 10 gives (-10, 0.0).  The two signals and the window have one length."""
+    n = _siglen(source)
+    if _siglen(target) != n or n < 1:
+        raise ValueError("block_delay needs two signals of one length of at least one sample (got %d and %d)" % (n, _siglen(target)))
+    lag, peak = xcorr_peaks(source, target, n, n, 0, 1, 1, window, window)
+    return lag[0] - n, peak[0]
+
+
+def maxdelwind(source, target, rate=1, start_time=0., delta_time=1., sample_duration=.5):
+    """delay, corr_strength, times = maxdelwind(source, target, rate, ...)
+
+    The delay from `source` to `target` as it changes over time: a block of `sample_duration` seconds every `delta_time`
+    seconds from `start_time` on (TransferFunctions.block_starts: the start is subtracted twice from the end, as the reference
+    does).  Both blocks lose their least-squares line, the target's is correlated against the source's over every lag:
+    delay [nblocks] is the lag of the largest correlation in seconds, minus sample_duration's samples (not minus one less:
+    block_delay's convention), corr_strength [nblocks] that correlation (float64 also for integer samples), times [nblocks] the
+    middle of every block.  No block: three empty arrays.  All blocks are one pass of pvx_xcorr_peak."""
+    n = min(_siglen(source), _siglen(target))
+    i0, sample_len, times = block_starts(n, rate, start_time, delta_time, sample_duration)
+    nblk = len(i0)
+    if nblk == 0:
+        _signals(source, target)
+        _lib.init()                                                   # host arithmetic, but no CPU fallback either
+        return np.zeros(0), np.zeros(0), times
+    if sample_len < 1:
+        raise ValueError("sample_duration must span at least one sample")
+    start, delta = int(i0[0]), (int(i0[1] - i0[0]) if nblk > 1 else 1)
+    lag, peak = xcorr_peaks(target, source, sample_len, sample_len, start, delta, nblk, detrend="linear")
+    return (lag - sample_len) / float(rate), peak, times
+
+
+def determineDelay(source, target, maxdel=2**16, ax=None):
+    """The delay between two signals in samples, from the extrema of their correlations over the first `maxdel` samples:
+    the arg-max of |correlate(target, source)| minus the arg-max of |correlate(source, source)|.  Two device calls.  `ax` (the
+    reference's plot) is not mirrored."""
+    if ax is not None:
+        raise NotImplementedError("determineDelay's plot (ax) is not mirrored (pypevoc/TransferFunctions.py:98-106; INTEGRATION.md)")
+    maxdel = int(maxdel)
+    _signals(source, target)
+    xd, yd = source[:maxdel], target[:maxdel]
+    lx, ly = _siglen(xd), _siglen(yd)
+    if lx < 1 or ly < 1:
+        raise ValueError("determineDelay needs at least one sample of each signal")
+    pkx, _ = xcorr_peaks(xd, xd, lx, lx, 0, 1, 1, use_abs=True)
+    pky, _ = xcorr_peaks(yd, xd, ly, lx, 0, 1, 1, use_abs=True)
+    return pky[0] - pkx[0]
