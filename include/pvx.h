@@ -116,8 +116,9 @@ int pvx_plan_device(const pvx_plan* plan);
 /* Which kernels the plan's last calls ran, as "analysis=<kernel>;synth=<kernel>" (a part is missing until its call has run):
  * k_fused_rev | k_fused_team | k_pv_rev | k_stft_pv | k_stft+k_phase_peaks | k_frames+rocfft+k_phase_peaks (the witness library
  * also k_fused | k_fused_mw | k_fused_ring | k_pv_team) for the analysis, k_synth_bodies<f64> | k_synth_bodies<f32> for the
- * resynthesis.  For tests and benchmarks that must know what they measured; the string lives in the plan and is valid until
- * its next call. */
+ * resynthesis.  k_fused_rev<kc8>: the instantiation of k_fused_rev that has the plan's npks (8) as a compile-time constant;
+ * plain k_fused_rev is the kernel for any npks (every other plan, or PVX_REV_NO_SPEC=1 in the environment).  For tests and
+ * benchmarks that must know what they measured; the string lives in the plan and is valid until its next call. */
 const char* pvx_plan_last_kernels(const pvx_plan* plan);
 /*
  * Progress reporting: replaces Progress.update (pypevoc/ProgressDisplay.py:82-88), which the

@@ -52,6 +52,13 @@ typedef unsigned short u16;
 #define PVX_RST(ptr, idx, val) __builtin_nontemporal_store((double)(val), &(ptr)[idx])
 #endif
 constexpr int kDense = 64;               // slots of the dense staging: one per lane of the per-peak pass
+// filter_by_salience's radius is a constant of this kernel: PV.py:177 hard-codes rad=5 and pvx_api.hip's analyze_rows() sets
+// FusedParams::rad = 5 at the only place such a block is filled; launch_fused_rev refuses any other value.  (As the run-time
+// p.rad its predicates and clamps were loop invariants held in spill lanes through the frame loop)
+constexpr int kRad = 5;
+static_assert(kRad >= 0 && kRad <= 5, "the one-candidate-per-lane branch reads five neighbours a side; salient_groups takes rad <= 8");
+// lanes of the per-peak pass per staged frame: the power of two at or above npks (64 at most); staged_frames() is 64 over it
+constexpr int lanes_per_frame(int K) { int l = 1; while (l < K && l < 64) l <<= 1; return l; }
 
 // FusedParams::wire: the result rows leave in the wire format of the multi-GPU gather (k_wire.hip: f float64 | mag float32 | ph float32 |
 // binno uint16 | totalmag float64, no realph -- the receiver rebuilds it with the expression above) instead of the reference's five
@@ -113,7 +120,10 @@ template <int R> struct RevGeo {
 // every second frame at npks 20, on signals whose frames keep 8 peaks.  Dense: a frame's kept peaks are staged behind the
 // previous frame's, the pass runs when the next frame might not fit (staged + npks > 64) or GFR frames wait: once per 6 frames
 // there.  The running slot count rides in bits 8.. of the loop's state word.
-template <int R, int NW, typename InT, bool AL2, int H, bool DENSE = false>
+// KC > 0: npks == KC, a constant of the instantiation (launch_rev picks it when the plan's npks is one of the instantiated
+// values); kpad, gs, LPF, the per-peak pass's lane / group split and the staging arrays' LDS offsets are then constants too
+// instead of scalars carried (in spill lanes) through the frame loop.  KC == 0: npks = p.K.  Same arithmetic either way.
+template <int R, int NW, typename InT, bool AL2, int H, bool DENSE = false, int KC = 0>
 __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
     using G = Geo<R>;
     using RG = RevGeo<R>;
@@ -122,9 +132,10 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int K = p.K;
+    const int K = KC > 0 ? KC : p.K;
     const int kpad = (K + 3) & ~3;
-    const int gs = staged_frames(K, GFR);
+    const int LPF = lanes_per_frame(K);                             // lanes of the per-peak pass per staged frame
+    const int gs = 64 / LPF < GFR ? 64 / LPF : GFR;                 // = staged_frames(K, GFR)
 
     v2f* const t1L = (v2f*)(smem + RG::OFF_T1);
     v2f* const t2L = (v2f*)(smem + RG::OFF_T2);
@@ -391,8 +402,6 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
     };
 
     // per-peak pass over this wave's staged frames [0, ng)
-    int LPF = 1;
-    while (LPF < K && LPF < 64) LPF <<= 1;
     auto flush = [&](int gbeg, int ng) {                           // groups [gbeg, ng)
         wave_sync();
         if constexpr (DENSE) {
@@ -401,7 +410,7 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
             kargs_t q = kargs;
             asm volatile("" : "+s"(q));
             PeakConst pc;
-            pc.fstep = q->fstep; pc.dt = q->dt; pc.nfft = G::N; pc.hop = q->hop; pc.wfbin = q->wfbin;
+            pc.fstep = q->fstep; pc.dt = q->dt; pc.nfft = G::N; pc.hop = H > 0 ? 128 * H : q->hop; pc.wfbin = q->wfbin;
             // (the frames' first slots and counts in ONE LDS round trip, then selects: a loop over the frames with a read each is a
             // chain of dependent round trips -- at nfft 1024 longer than the transform it sits beside)
             static_assert(GFR == 8, "two 16-byte reads per table");
@@ -480,7 +489,7 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
         asm volatile("" : "+s"(q));                                  // loads through q stay here
         const bool wire = q->wire != 0;
         PeakConst pc;
-        pc.fstep = q->fstep; pc.dt = q->dt; pc.nfft = G::N; pc.hop = q->hop; pc.wfbin = q->wfbin;
+        pc.fstep = q->fstep; pc.dt = q->dt; pc.nfft = G::N; pc.hop = H > 0 ? 128 * H : q->hop; pc.wfbin = q->wfbin;
         const int g = gbeg + gl;
         const bool gvalid = g < ng;
         const int cnt = gvalid ? Lcnt[g] : -1;
@@ -543,7 +552,7 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
         gq = g - gb * rows1;
         if (g >= 0 && gq >= 1) { csrc = row_ptr(gb, gq); orow = gb * Fi + gq - 1; }
     }
-    const int hopi = p.hop;
+    const int hopi = H > 0 ? 128 * H : p.hop;                        // (H > 0: the launcher picked H from hop == 128 H)
     if (!idle_wave && g >= glast && g >= 0 && gq >= 1) { prefetch_part(csrc, 0); prefetch_part(csrc, 1); prefetch_part(csrc, 2); prefetch_part(csrc, 3); }
     // (the first row's samples are on their way from HBM while the workgroup fills its tables: two latencies side by side --
     // every launch pays them once per wave, and BASELINE config 2 is one launch of 17 rows per wave)
@@ -681,7 +690,7 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
             }
             wave_sync();
             __builtin_amdgcn_s_setprio(PVX_PRIO_C);
-            if (C <= 64 && p.rad <= 5 && !(th < 0.0 && C < K)) {
+            if (C <= 64 && !(th < 0.0 && C < K)) {
                 // ---- at most one candidate per lane (every frame of music): lane c owns candidate c and fetches
                 // in ONE LDS round trip all that the rest of the frame needs of it -- its score, the 2*rad
                 // neighbours of the salience test (PF.py:126-134; indices clamped into the window like `salient`),
@@ -692,7 +701,7 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
                 // (a lane without a candidate keeps nothing, whatever it reads.  nfft 2048: it reads around bin 8, not bin 1 -- bin 1 would
                 // fail the interior ballot below on every frame with fewer than 64 candidates)
                 const int pb = has ? (int)Lci[lane] : (X4 ? 8 : 1);
-                const int rad = p.rad;
+                constexpr int rad = kRad;
                 const int lo = pb - rad > 1 ? pb - rad : 1;
                 int hi = pb + rad < M ? pb + rad : M;
                 hi = hi > M - 1 ? M - 1 : hi;
@@ -797,10 +806,8 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
                 int pb = 0;
                 if (e < nsel) pb = Lsel[e];
                 bool keep;
-                if constexpr (X4) keep = (p.rad <= 8) ? salient_groups<0>(YofX4{cur}, M, Lsel, eb, nsel, p.rad, lane)
-                                                      : ((e < nsel) && salient<float, 0>(YofX4{cur}, M, pb, p.rad));
-                else keep = (p.rad <= 8) ? salient_groups<1>(Ly, M, Lsel, eb, nsel, p.rad, lane)
-                                         : ((e < nsel) && salient<float, 1>(Ly, M, pb, p.rad));
+                if constexpr (X4) keep = salient_groups<0>(YofX4{cur}, M, Lsel, eb, nsel, kRad, lane);
+                else keep = salient_groups<1>(Ly, M, Lsel, eb, nsel, kRad, lane);
                 const unsigned long long bal = __ballot(keep);
                 if (keep) {
                     const int sl = (DENSE ? (int)(st / ST_NST) : ng * kpad) + nk + lane_prefix(bal);
@@ -875,8 +882,16 @@ __global__ __launch_bounds__(64 * NW) void k_fused_rev(FusedParams p) {
     }
 }
 
-template <int R, int NW, bool DENSE = false> int launch_rev(const FusedParams& p, int x_dtype, hipStream_t s, size_t* stash_need = nullptr) {
+// SPEC: this (R, NW) has an instantiation with npks as a constant (the kernel's KC): 8, the npks of every BASELINE configuration
+// from 2 on; a plan with that npks runs it, any other the generic kernel.  PVX_REV_NO_SPEC=1: the generic kernel always (A/B runs,
+// tests).  *kc: the KC launched.  +1.3 ... 4.2 % over the generic kernel at every nfft, tone and noise.  (KC = 20, the reference's
+// default npks, for the dense staging: measured, 0 % on a tone and +1 % on noise -- not instantiated; profiles/rev_spec_ab.jsonl.)
+template <int R, int NW, bool DENSE = false, bool SPEC = false> int launch_rev(const FusedParams& p, int x_dtype, hipStream_t s, size_t* stash_need = nullptr, int* kc = nullptr) {
     using RG = RevGeo<R>;
+    static_assert(!(SPEC && DENSE), "npks 8 takes the strided staging");
+    constexpr int KCS = SPEC ? 8 : 0;
+    const bool spec = SPEC && p.K == KCS && getenv("PVX_REV_NO_SPEC") == nullptr;
+    if (kc) *kc = spec ? KCS : 0;
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess) {
         int v = 0;
@@ -888,7 +903,8 @@ template <int R, int NW, bool DENSE = false> int launch_rev(const FusedParams& p
     const bool al2 = (x_dtype == PVX_F32) && (p.hop % 2 == 0) && (p.sig_stride % 2 == 0) && (((uintptr_t)p.x) % 8 == 0);
     const int H = (p.hop == 32 * R) ? R / 4 : (p.hop == 64 * R) ? R / 2 : 0;
     const void* fn = nullptr;
-#define PVX_REV_PICK(INT, AL) (H == R / 4 ? (const void*)k_fused_rev<R, NW, INT, AL, R / 4, DENSE> : H ? (const void*)k_fused_rev<R, NW, INT, AL, R / 2, DENSE> : (const void*)k_fused_rev<R, NW, INT, AL, 0, DENSE>)
+#define PVX_REV_PICK_KC(INT, AL, KC) (H == R / 4 ? (const void*)k_fused_rev<R, NW, INT, AL, R / 4, DENSE, KC> : H ? (const void*)k_fused_rev<R, NW, INT, AL, R / 2, DENSE, KC> : (const void*)k_fused_rev<R, NW, INT, AL, 0, DENSE, KC>)
+#define PVX_REV_PICK(INT, AL) (spec ? PVX_REV_PICK_KC(INT, AL, KCS) : PVX_REV_PICK_KC(INT, AL, 0))
     switch (x_dtype) {
         // (the dense staging's instantiations do without the 8-byte sample loads: a row's new samples are a quarter of its loads)
         case PVX_F32: if constexpr (DENSE) { fn = PVX_REV_PICK(float, false); } else { fn = al2 ? PVX_REV_PICK(float, true) : PVX_REV_PICK(float, false); } break;
@@ -896,6 +912,7 @@ template <int R, int NW, bool DENSE = false> int launch_rev(const FusedParams& p
         default: pvx_set_error("the fused kernels take float32 or int16 samples (x_dtype %d: float64 is narrowed before the launch)", x_dtype); return PVX_ERR_INVALID;
     }
 #undef PVX_REV_PICK
+#undef PVX_REV_PICK_KC
     if (lds > 64 * 1024) PVX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int blocks_per_cu = (int)((160 * 1024) / lds);
     if (blocks_per_cu < 1) blocks_per_cu = 1;
@@ -933,15 +950,17 @@ int pvx_fused_rev_supported(int nfft, int precision, int K) {
     }
 }
 
-static int launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s, size_t* stash_need);
-int pvx_launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s) { return launch_fused_rev(p, nfft, x_dtype, s, nullptr); }
+static int launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s, size_t* stash_need, int* kc);
+int pvx_launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s, int* kc) { return launch_fused_rev(p, nfft, x_dtype, s, nullptr, kc); }
 size_t pvx_fused_rev_stash_bytes(const FusedParams& p, int nfft) {
     size_t need = 0;
-    if (launch_fused_rev(p, nfft, PVX_F32, nullptr, &need) != PVX_OK) return 0;
+    if (launch_fused_rev(p, nfft, PVX_F32, nullptr, &need, nullptr) != PVX_OK) return 0;
     return need;
 }
-static int launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s, size_t* stash_need) {
+static int launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s, size_t* stash_need, int* kc) {
     if (stash_need) *stash_need = 0;
+    if (kc) *kc = 0;
+    if (p.rad != kRad) { pvx_set_error("the fused kernel filters by salience at radius %d only (rad=%d)", kRad, p.rad); return PVX_ERR_UNSUPPORTED; }
     if (p.total_rows <= 0) return PVX_OK;
     // 8 < npks <= 24: the kept peaks staged densely (see the kernel's DENSE; from 25 on two full frames are all that fit either way, and the
     // dense pass is the dearer one: -3 % on a recording at npks 32); PVX_REV_NO_DENSE=1: the strided staging (A/B, tests)
@@ -956,9 +975,10 @@ static int launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStre
     }
     switch (nfft) {
         // three waves per SIMD when the waves' buffers fit (npks up to ~90), else two
-        case 2048: return (RevGeo<16>::total(p.K, 12) <= 160 * 1024 && getenv("PVX_REV_NW8") == nullptr) ? launch_rev<16, 12>(p, x_dtype, s, stash_need) : launch_rev<16, 8>(p, x_dtype, s, stash_need);
-        case 1024: return launch_rev<8, PVX_REV_NW1024>(p, x_dtype, s, stash_need);
-        case 512: return RevGeo<4>::total(p.K, PVX_REV_NW512) <= 160 * 1024 ? launch_rev<4, PVX_REV_NW512>(p, x_dtype, s, stash_need) : launch_rev<4, 12>(p, x_dtype, s, stash_need);
+        // (the instantiations with npks as a constant are those of the wave counts npks 8 runs at; the fall-backs stay generic)
+        case 2048: return (RevGeo<16>::total(p.K, 12) <= 160 * 1024 && getenv("PVX_REV_NW8") == nullptr) ? launch_rev<16, 12, false, true>(p, x_dtype, s, stash_need, kc) : launch_rev<16, 8>(p, x_dtype, s, stash_need);
+        case 1024: return launch_rev<8, PVX_REV_NW1024, false, true>(p, x_dtype, s, stash_need, kc);
+        case 512: return RevGeo<4>::total(p.K, PVX_REV_NW512) <= 160 * 1024 ? launch_rev<4, PVX_REV_NW512, false, true>(p, x_dtype, s, stash_need, kc) : launch_rev<4, 12>(p, x_dtype, s, stash_need);
         default: pvx_set_error("the fused kernel does not handle nfft=%d", nfft); return PVX_ERR_UNSUPPORTED;
     }
 }

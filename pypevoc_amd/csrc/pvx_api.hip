@@ -168,6 +168,7 @@ struct pvx_plan {
     Route general = Route::frames_rocfft;  // fft mode 0's route for the plan's shape and creation-time switches (route_for narrows
                                            // it per call); all but frames_rocfft have k_stft write d_spec (has_stft)
     Route last_route = Route::none;        // kernels of the last calls (pvx_plan_last_kernels)
+    int last_rev_kc = 0;                   // k_fused_rev: the npks its instantiation had as a constant (0: the generic kernel)
     const char* last_synth = nullptr;
     std::string last_kernels;
     int64_t ldi = 0, ldo = 0; // workspace row pitches (elements / complex elements)
@@ -254,6 +255,7 @@ extern "C" const char* pvx_plan_last_kernels(const pvx_plan* plan) {
     pvx_plan* p = const_cast<pvx_plan*>(plan);
     p->last_kernels.clear();
     if (p->last_route != Route::none) { p->last_kernels += "analysis="; p->last_kernels += kRouteName[(int)p->last_route]; }
+    if (p->last_route == Route::fused_rev && p->last_rev_kc > 0) p->last_kernels += "<kc" + std::to_string(p->last_rev_kc) + ">";   // (npks a constant of the kernel)
     if (p->last_synth) { if (!p->last_kernels.empty()) p->last_kernels += ";"; p->last_kernels += "synth="; p->last_kernels += p->last_synth; }
     return p->last_kernels.c_str();
 }
@@ -685,7 +687,7 @@ static int analyze_rows(pvx_plan* p, Route route, const void* d_x, int x_dtype, 
             case Route::fused_mw: rc = pvx_launch_fused_mw(fp, p->nfft, x_dtype, s); break;
             case Route::fused_ring: rc = pvx_launch_fused_ring(fp, p->nfft, x_dtype, s); break;
             case Route::fused_team: rc = pvx_launch_fused_team(fp, p->nfft, x_dtype, s); break;
-            default: rc = pvx_launch_fused_rev(fp, p->nfft, x_dtype, s); break;
+            default: rc = pvx_launch_fused_rev(fp, p->nfft, x_dtype, s, &p->last_rev_kc); break;
         }
         return rc != PVX_OK ? rc : plan_event(p, s, -1);
     }

@@ -123,7 +123,8 @@ int pvx_launch_fused_mw(const FusedParams& p, int nfft, int x_dtype, hipStream_t
 int pvx_fused_ring_supported(int nfft, int precision, int K);   // k_fused_ring.hip: workgroup-shared spectrum ring
 int pvx_launch_fused_ring(const FusedParams& p, int nfft, int x_dtype, hipStream_t s);
 int pvx_fused_rev_supported(int nfft, int precision, int K);    // k_fused_rev.hip: independent waves, rows in descending order
-int pvx_launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s);
+// (*kc: the npks the launched instantiation has as a constant, 0 for the generic kernel -- pvx_plan_last_kernels' <kcN> suffix)
+int pvx_launch_fused_rev(const FusedParams& p, int nfft, int x_dtype, hipStream_t s, int* kc = nullptr);
 int pvx_fused_team_supported(int nfft, int precision, int K);   // k_fused_team.hip: nfft 4096 / 8192 as teams of k_fused_rev-shaped waves
 int pvx_launch_fused_team(const FusedParams& p, int nfft, int x_dtype, hipStream_t s);
 int pvx_fused_team_table_len(int nfft);                          // complex entries it wants appended to the W_nfft^j table

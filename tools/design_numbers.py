@@ -121,7 +121,7 @@ if sw:
 s64 = jl("%s_config5_sweep_f64.jsonl" % tag)
 if s64:
     p64 = {(d["nfft"], d["hop"]): d for d in jl("%s_config5_sweep_f64.jsonl" % prev)}
-    L.append("**Config 5 at float64** (`profiles/%s_config5_sweep_f64.jsonl`, M frames/s; round 5 in brackets): " % tag +
+    L.append("**Config 5 at float64** (`profiles/%s_config5_sweep_f64.jsonl`, M frames/s; round %d in brackets): " % (tag, int(prev[1:])) +
              ", ".join("%d/%d %s%s" % (d["nfft"], d["hop"], M(d["frames_per_s"]).replace(" M", ""), (" (%s)" % M(p64[(d["nfft"], d["hop"])]["frames_per_s"]).replace(" M", "")) if (d["nfft"], d["hop"]) in p64 else "") for d in s64) + ".")
     L.append("")
 hn = []       # (`profiles/<tag>_nfft_harmonic_vs_noise.jsonl`: the nfft sweep on three kinds of material; the bench table above carries the noise / recording lines)
