@@ -654,6 +654,45 @@ int64_t pvx_formants_dev(const void* d_x, int x_dtype, int64_t n, int preemph, i
                          void* stream);
 const char* pvx_formants_last_kernels(void);
 
+/* ---- LPC spectral envelopes and refined peaks (pypevoc/speech/SpeechAnalysis.py: lpc2form_full :211-218;
+ *      pypevoc/PeakFinder.py: findpos :155-194 with the default thresholds, refine :331-372, refine_all :374-413;
+ *      ENVELOPE.md) ----
+ *
+ * pvx_lpc_envelope: for each of n coefficient rows coef[i][0 .. order] (pvx_formants' lpc rows, [1, a_1 .. a_order]; coef[i][0]
+ * need not be 1, a zero there is PVX_ERR_INVALID) the envelope y_k = 1 / |sum_j coef[i][j] z_k^j|, z_k = exp(-i pi k / npts),
+ * k < npts -- abs(freqz([1], coef[i], worN=npts)[1]) --, one wave per row.  Its peaks are the indices 1 <= k <= npts - 2 with
+ * y[k-1] < y[k] >= y[k+1] (a NaN compares false), ascending; each is refined through its two neighbours: c = y[k],
+ * b = (y[k+1] - y[k-1]) / 2, a = (y[k+1] + y[k-1]) / 2 - c, lpos = -b / 2 / a, val = a lpos^2 + b lpos + c and pos =
+ * np.interp(k + lpos, arange(npts), x) on the axis x_k = k fs / (2 npts).  Outputs, each nullable: env [n][npts]; npk [n], a
+ * row's number of peaks; idx [n][maxpk], -1 beyond npk; pos, val [n][maxpk], NaN beyond npk.  A row with more than maxpk peaks
+ * makes the call return PVX_ERR_SIZE with the first such row in *overflow_row (nullable; -1 otherwise): its first maxpk peaks
+ * are written and npk holds its full count (idx, pos and val all null: nothing can overflow).  A root on the unit circle at a
+ * grid point gives inf there, as in scipy: not handled.
+ *
+ * pvx_peaks_refine: the same scan and refinement on n rows y[i][0 .. npts) with the axis x[npts] (null: arange(npts)).  With
+ * sel [n][maxpk], int32 and -1 padded, the scan is skipped and the given indices are refined slot by slot (npk: the slots that
+ * are not -1), the fit where y[k] > y[k-1] and y[k] >= y[k+1], else refine's other branch: pos = x[k], val = y[k].  A given
+ * index outside 1 .. npts - 2 is PVX_ERR_INVALID.
+ *
+ * Limits: 1 <= order <= PVX_ROOTS_MAX_ORDER and 1 <= npts <= PVX_ENV_MAX_NPTS, else PVX_ERR_UNSUPPORTED and no launch; npts < 3,
+ * n < 0 or maxpk < 0 is PVX_ERR_INVALID.  n = 0 launches nothing.  float64 throughout; a point's value depends on its row and
+ * index alone.  Host rows are processed in groups of whole rows sized by PVX_MAX_DEVICE_BYTES (per buffer): a row's bits do not
+ * depend on the grouping, on its place in the batch or on where the input came from.  The _dev forms take device memory for
+ * every array, work on `stream` and are synchronised before they return.  All four return n or a negative status.
+ * pvx_envelope_last_kernels: what the calling thread's last call of the four ran ("k_lpc_envelope", "k_peaks_refine"; "" when
+ * it launched nothing).
+ */
+#define PVX_ENV_MAX_NPTS 16384
+int64_t pvx_lpc_envelope(const double* coef, int64_t n, int order, int npts, double fs, int maxpk, double* env, int32_t* npk, int32_t* idx,
+                         double* pos, double* val, int64_t* overflow_row);
+int64_t pvx_lpc_envelope_dev(const double* d_coef, int64_t n, int order, int npts, double fs, int maxpk, double* d_env, int32_t* d_npk,
+                             int32_t* d_idx, double* d_pos, double* d_val, int64_t* overflow_row, void* stream);
+int64_t pvx_peaks_refine(const double* y, int64_t n, int npts, const double* x, int maxpk, const int32_t* sel, int32_t* npk, int32_t* idx,
+                         double* pos, double* val, int64_t* overflow_row);
+int64_t pvx_peaks_refine_dev(const double* d_y, int64_t n, int npts, const double* d_x, int maxpk, const int32_t* d_sel, int32_t* d_npk,
+                             int32_t* d_idx, double* d_pos, double* d_val, int64_t* overflow_row, void* stream);
+const char* pvx_envelope_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

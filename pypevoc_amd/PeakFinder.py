@@ -1,8 +1,9 @@
 """Drop-in mirror of pypevoc.PeakFinder.PeakFinder for the part the phase vocoder uses
-(pypevoc/PeakFinder.py:35-74 ctor, 155-194 findpos, 113-136 filter_by_salience, 76-111 properties).
+(pypevoc/PeakFinder.py:35-74 ctor, 155-194 findpos, 113-136 filter_by_salience, 76-111 properties), and for
+the three-point refinement (331-372 refine, 374-413 refine_all).
 
-Peak selection and the salience filter run in libpvx_hip (one wave64 per row, k_peaks.hip); the
-refinement / prominence / area helpers of the reference are outside the hot path and not mirrored.
+Peak selection and the salience filter run in libpvx_hip (one wave64 per row, k_peaks.hip), the refinement too
+(k_lpcenv.hip, ENVELOPE.md); refine_opt and the prominence / area helpers of the reference are not mirrored.
 """
 import numpy as np
 
@@ -154,6 +155,38 @@ class PeakFinder(object):
     def get_pos(self):
         return self.pos
 
+    def _refine_rows(self, y, sel):
+        """pvx_peaks_refine (k_lpcenv.hip, ENVELOPE.md) on the one row y with the peak indices sel: pos, val."""
+        from .speech import envelope
+        sel = np.asarray(sel, dtype=np.int32).reshape(1, -1)
+        _, _, pos, val = envelope.peaks_frames(np.asarray(y, dtype=np.float64)[None, :], np.asarray(self.x, dtype=np.float64), sel=sel)
+        return pos[0], val[0]
+
+    def refine(self, idx, fun=None, yvec=None):
+        """Quadratic interpolation through a peak and its two neighbours (PeakFinder.py:331-372): the fine position on the
+        x axis and the fine value of peak number idx.  fun (a warping function solved for with scipy.optimize) is not
+        mirrored."""
+        if fun:
+            raise NotImplementedError("PeakFinder.refine(fun=...) (PeakFinder.py:345-363) is not mirrored by pypevoc_amd; use the "
+                                      "reference class for it (see INTEGRATION.md, 'not mirrored')")
+        pos, val = self._refine_rows(self.y if yvec is None else yvec, [self._idx[idx]])
+        return pos[0], float(val[0])
+
+    def refine_all(self, logarithmic=False, rad=1):
+        """Refine all peaks by quadratic interpolation (PeakFinder.py:374-413), one device call for the row.  rad > 1
+        (refine_opt's polynomial fit) is not mirrored."""
+        if rad > 1:
+            raise NotImplementedError("PeakFinder.refine_all(rad > 1) needs refine_opt (PeakFinder.py:304-329), which is not "
+                                      "mirrored by pypevoc_amd; use the reference class for it (see INTEGRATION.md, 'not mirrored')")
+        y = np.log10(self.y) if logarithmic else self.y
+        self._fine_pos = np.zeros(self._idx.shape)
+        self._fine_val = np.zeros(self._idx.shape)
+        if len(self._idx) == 0:
+            return
+        pos, val = self._refine_rows(y, self._idx)
+        self._fine_pos[:] = pos
+        self._fine_val[:] = 10 ** val if logarithmic else val
+
 
 def _unsupported(name, where):
     def method(self, *args, **kwargs):
@@ -165,10 +198,9 @@ def _unsupported(name, where):
     return method
 
 
-# sub-sample refinement, areas, prominence and export helpers of the reference class: named here so that a caller
+# the polynomial-fit refinement, areas, prominence and export helpers of the reference class: named here so that a caller
 # gets a clear NotImplementedError instead of an AttributeError
-for _n, _w in (("refine", "PeakFinder.py:331-372"), ("refine_opt", "PeakFinder.py:304-329"), ("refine_all", "PeakFinder.py:374-413"),
-               ("get_areas", "PeakFinder.py:415-437"), ("find_prominence", "PeakFinder.py:196-221"),
+for _n, _w in (("refine_opt", "PeakFinder.py:304-329"), ("get_areas", "PeakFinder.py:415-437"), ("find_prominence", "PeakFinder.py:196-221"),
                ("filter_by_prominence", "PeakFinder.py:138-153"), ("to_dict", "PeakFinder.py:439-473"), ("plot", "PeakFinder.py:223-267")):
     setattr(PeakFinder, _n, _unsupported("PeakFinder." + _n, _w))
 

@@ -15,6 +15,7 @@ PVX_SYNTH_NO_PHCOR = 1
 PVX_SYNTH_F32 = 2
 PVX_ERR_SIZE = -6            # include/pvx.h
 PVX_ERR_UNSUPPORTED = -5
+PVX_ERR_INVALID = -2
 PVX_ERR_SINGULAR = -7
 PVX_ERR_NOCONV = -8
 PVX_F32, PVX_F64, PVX_I16 = 0, 1, 2
@@ -180,6 +181,15 @@ SIGNATURES = {
                                           c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double] +
                          [ctypes.c_void_p] * 6 + [c_int64_p, c_int64_p, ctypes.c_void_p]),
     "pvx_formants_last_kernels": (ctypes.c_char_p, []),
+    "pvx_lpc_envelope": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p,
+                                          c_int32_p, c_int32_p, c_double_p, c_double_p, c_int64_p]),
+    "pvx_lpc_envelope_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int] +
+                             [ctypes.c_void_p] * 5 + [c_int64_p, ctypes.c_void_p]),
+    "pvx_peaks_refine": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, ctypes.c_int, c_int32_p, c_int32_p, c_int32_p,
+                                          c_double_p, c_double_p, c_int64_p]),
+    "pvx_peaks_refine_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
+                             [ctypes.c_void_p] * 5 + [c_int64_p, ctypes.c_void_p]),
+    "pvx_envelope_last_kernels": (ctypes.c_char_p, []),
 }
 
 

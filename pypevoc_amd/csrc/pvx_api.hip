@@ -2890,6 +2890,172 @@ extern "C" int64_t pvx_polyroots_dev(const double* d_coef, int64_t n, int order,
     return polyroots_body<true>(d_coef, n, order, d_re, d_im, d_nkept, d_status, noconv_row, (hipStream_t)stream);
 }
 
+// ---- LPC spectral envelopes and refined peaks (k_lpcenv.hip) -------------------------------
+static thread_local const char* t_envelope_kernels = "";
+extern "C" const char* pvx_envelope_last_kernels(void) { return t_envelope_kernels; }
+
+static int envelope_limits(const char* what, int64_t n, int order, int npts, int maxpk) {
+    if (order < 1 || order > PVX_ROOTS_MAX_ORDER || npts < 1 || npts > PVX_ENV_MAX_NPTS) {
+        pvx_set_error("%s: order %d, npts %d: the kernel takes orders 1 .. %d and 3 .. %d points", what, order, npts, PVX_ROOTS_MAX_ORDER,
+                      PVX_ENV_MAX_NPTS);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    if (npts < 3 || n < 0 || maxpk < 0) { pvx_set_error("bad %s argument (npts >= 3, n >= 0, maxpk >= 0)", what); return PVX_ERR_INVALID; }
+    return PVX_OK;
+}
+
+// the device lists of a group of rows of a host call, and their way back
+struct PeakLists {
+    DevMem k, i, p, v;
+    int alloc(size_t rows, size_t maxpk, bool npk, bool idx, bool pos, bool val) {
+        int rc;
+        if ((npk && (rc = k.alloc(rows * 4)) != PVX_OK) || (idx && (rc = i.alloc(rows * maxpk * 4)) != PVX_OK) ||
+            (pos && (rc = p.alloc(rows * maxpk * 8)) != PVX_OK) || (val && (rc = v.alloc(rows * maxpk * 8)) != PVX_OK)) return rc;
+        return PVX_OK;
+    }
+};
+
+static int peak_lists_to_host(const PeakLists& d, size_t o, size_t k, size_t maxpk, int32_t* npk, int32_t* idx, double* pos, double* val) {
+    int rc;
+    if ((npk && (rc = device_to_host(npk + o, d.k.get(), k * 4)) != PVX_OK) ||
+        (idx && maxpk && (rc = device_to_host(idx + o * maxpk, d.i.get(), k * maxpk * 4)) != PVX_OK) ||
+        (pos && maxpk && (rc = device_to_host(pos + o * maxpk, d.p.get(), k * maxpk * 8)) != PVX_OK) ||
+        (val && maxpk && (rc = device_to_host(val + o * maxpk, d.v.get(), k * maxpk * 8)) != PVX_OK)) return rc;
+    return PVX_OK;
+}
+
+// Rows in groups sized by PVX_MAX_DEVICE_BYTES (per buffer, as polyroots_body): a row's bits depend on the row alone.
+template <bool DEV>
+static int64_t lpc_envelope_body(const double* coef, int64_t n, int order, int npts, double fs, int maxpk, double* env, int32_t* npk,
+                                 int32_t* idx, double* pos, double* val, int64_t* overflow_row, hipStream_t s) {
+    if (overflow_row) *overflow_row = -1;
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_envelope_kernels = "";
+    if ((rc = envelope_limits("pvx_lpc_envelope", n, order, npts, maxpk)) != PVX_OK) return rc;
+    if (n == 0) return 0;
+    if (!coef) { pvx_set_error("null pvx_lpc_envelope coefficients"); return PVX_ERR_INVALID; }
+    const size_t P = (size_t)order, N = (size_t)npts, K = (size_t)maxpk, rb = (P + 1) * 8;
+    if (!DEV)
+        for (int64_t i = 0; i < n; i++)
+            if (coef[(size_t)i * (P + 1)] == 0.0) { pvx_set_error("pvx_lpc_envelope: row %lld has a zero leading coefficient", (long long)i); return PVX_ERR_INVALID; }
+    int64_t own = n;
+    DevMem dc, de;
+    PeakLists dl;
+    if (!DEV) {
+        own = std::min(n, std::max<int64_t>(1, (int64_t)(iaif_limit() / std::max(std::max(rb, K * 8), env ? N * 8 : (size_t)8))));
+        if ((rc = dc.alloc((size_t)own * rb)) != PVX_OK || (env && (rc = de.alloc((size_t)own * N * 8)) != PVX_OK) ||
+            (rc = dl.alloc((size_t)own, K, npk != nullptr, idx != nullptr, pos != nullptr, val != nullptr)) != PVX_OK) return rc;
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += own) {
+        const int64_t cnt = std::min(own, n - r0);
+        const size_t o = (size_t)r0, k = (size_t)cnt;
+        int64_t over = -1, bad = -1;
+        if (!DEV) {
+            if ((rc = host_to_device(dc.get(), coef + o * (P + 1), k * rb)) != PVX_OK) return rc;
+            rc = pvx_lpcenv_run(dc.as<double>(), cnt, order, npts, fs, maxpk, env ? de.as<double>() : nullptr, npk ? dl.k.as<int>() : nullptr,
+                                idx ? dl.i.as<int>() : nullptr, pos ? dl.p.as<double>() : nullptr, val ? dl.v.as<double>() : nullptr, &over, &bad,
+                                s, &t_envelope_kernels);
+        } else {
+            rc = pvx_lpcenv_run(coef + o * (P + 1), cnt, order, npts, fs, maxpk, env ? env + o * N : nullptr, npk ? npk + o : nullptr,
+                                idx ? idx + o * K : nullptr, pos ? pos + o * K : nullptr, val ? val + o * K : nullptr, &over, &bad, s,
+                                &t_envelope_kernels);
+        }
+        if (rc != PVX_OK) return rc;
+        if (!DEV) {
+            if ((env && (rc = device_to_host(env + o * N, de.get(), k * N * 8)) != PVX_OK) ||
+                (rc = peak_lists_to_host(dl, o, k, K, npk, idx, pos, val)) != PVX_OK) return rc;
+        }
+        if (bad >= 0) {
+            pvx_set_error("pvx_lpc_envelope: row %lld has a zero leading coefficient", (long long)(r0 + bad));
+            return PVX_ERR_INVALID;
+        }
+        if (over >= 0) {
+            if (overflow_row) *overflow_row = r0 + over;
+            pvx_set_error("pvx_lpc_envelope: row %lld has more than maxpk = %d peaks", (long long)(r0 + over), maxpk);
+            return PVX_ERR_SIZE;
+        }
+    }
+    return n;
+}
+
+extern "C" int64_t pvx_lpc_envelope(const double* coef, int64_t n, int order, int npts, double fs, int maxpk, double* env, int32_t* npk,
+                                    int32_t* idx, double* pos, double* val, int64_t* overflow_row) {
+    return lpc_envelope_body<false>(coef, n, order, npts, fs, maxpk, env, npk, idx, pos, val, overflow_row, nullptr);
+}
+
+extern "C" int64_t pvx_lpc_envelope_dev(const double* d_coef, int64_t n, int order, int npts, double fs, int maxpk, double* d_env,
+                                        int32_t* d_npk, int32_t* d_idx, double* d_pos, double* d_val, int64_t* overflow_row, void* stream) {
+    return lpc_envelope_body<true>(d_coef, n, order, npts, fs, maxpk, d_env, d_npk, d_idx, d_pos, d_val, overflow_row, (hipStream_t)stream);
+}
+
+template <bool DEV>
+static int64_t peaks_refine_body(const double* y, int64_t n, int npts, const double* x, int maxpk, const int32_t* sel, int32_t* npk,
+                                 int32_t* idx, double* pos, double* val, int64_t* overflow_row, hipStream_t s) {
+    if (overflow_row) *overflow_row = -1;
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    t_envelope_kernels = "";
+    if ((rc = envelope_limits("pvx_peaks_refine", n, 1, npts, maxpk)) != PVX_OK) return rc;
+    if (n == 0) return 0;
+    if (!y) { pvx_set_error("null pvx_peaks_refine rows"); return PVX_ERR_INVALID; }
+    const size_t N = (size_t)npts, K = (size_t)maxpk;
+    if (!DEV && sel)
+        for (size_t t = 0; t < (size_t)n * K; t++)
+            if (sel[t] != -1 && (sel[t] < 1 || sel[t] > npts - 2)) {
+                pvx_set_error("pvx_peaks_refine: row %lld: index %d is outside 1 .. npts - 2", (long long)(t / K), (int)sel[t]);
+                return PVX_ERR_INVALID;
+            }
+    int64_t own = n;
+    DevMem dy, dx, ds;
+    PeakLists dl;
+    if (!DEV) {
+        own = std::min(n, std::max<int64_t>(1, (int64_t)(iaif_limit() / std::max(N * 8, K * 8))));
+        if ((rc = dy.alloc((size_t)own * N * 8)) != PVX_OK || (x && (rc = dx.alloc(N * 8)) != PVX_OK) ||
+            (sel && (rc = ds.alloc((size_t)own * K * 4)) != PVX_OK) ||
+            (rc = dl.alloc((size_t)own, K, npk != nullptr, idx != nullptr, pos != nullptr, val != nullptr)) != PVX_OK) return rc;
+        if (x && (rc = host_to_device(dx.get(), x, N * 8)) != PVX_OK) return rc;
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += own) {
+        const int64_t cnt = std::min(own, n - r0);
+        const size_t o = (size_t)r0, k = (size_t)cnt;
+        int64_t over = -1, bad = -1;
+        if (!DEV) {
+            if ((rc = host_to_device(dy.get(), y + o * N, k * N * 8)) != PVX_OK ||
+                (sel && K && (rc = host_to_device(ds.get(), sel + o * K, k * K * 4)) != PVX_OK)) return rc;
+            rc = pvx_peaks_refine_run(dy.as<double>(), cnt, npts, x ? dx.as<double>() : nullptr, maxpk, sel ? ds.as<int>() : nullptr,
+                                      npk ? dl.k.as<int>() : nullptr, idx ? dl.i.as<int>() : nullptr, pos ? dl.p.as<double>() : nullptr,
+                                      val ? dl.v.as<double>() : nullptr, &over, &bad, s, &t_envelope_kernels);
+        } else {
+            rc = pvx_peaks_refine_run(y + o * N, cnt, npts, x, maxpk, sel ? sel + o * K : nullptr, npk ? npk + o : nullptr,
+                                      idx ? idx + o * K : nullptr, pos ? pos + o * K : nullptr, val ? val + o * K : nullptr, &over, &bad, s,
+                                      &t_envelope_kernels);
+        }
+        if (rc != PVX_OK) return rc;
+        if (!DEV && (rc = peak_lists_to_host(dl, o, k, K, npk, idx, pos, val)) != PVX_OK) return rc;
+        if (bad >= 0) {
+            pvx_set_error("pvx_peaks_refine: row %lld: a given index is outside 1 .. npts - 2", (long long)(r0 + bad));
+            return PVX_ERR_INVALID;
+        }
+        if (over >= 0) {
+            if (overflow_row) *overflow_row = r0 + over;
+            pvx_set_error("pvx_peaks_refine: row %lld has more than maxpk = %d peaks", (long long)(r0 + over), maxpk);
+            return PVX_ERR_SIZE;
+        }
+    }
+    return n;
+}
+
+extern "C" int64_t pvx_peaks_refine(const double* y, int64_t n, int npts, const double* x, int maxpk, const int32_t* sel, int32_t* npk,
+                                    int32_t* idx, double* pos, double* val, int64_t* overflow_row) {
+    return peaks_refine_body<false>(y, n, npts, x, maxpk, sel, npk, idx, pos, val, overflow_row, nullptr);
+}
+
+extern "C" int64_t pvx_peaks_refine_dev(const double* d_y, int64_t n, int npts, const double* d_x, int maxpk, const int32_t* d_sel,
+                                        int32_t* d_npk, int32_t* d_idx, double* d_pos, double* d_val, int64_t* overflow_row, void* stream) {
+    return peaks_refine_body<true>(d_y, n, npts, d_x, maxpk, d_sel, d_npk, d_idx, d_pos, d_val, overflow_row, (hipStream_t)stream);
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

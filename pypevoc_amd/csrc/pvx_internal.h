@@ -399,6 +399,14 @@ int pvx_formants_run(const FormantCall& c, const void* d_x, int64_t x0, int64_t 
 int pvx_polyroots_run(const double* d_coef, int64_t n, int order, double* d_re, double* d_im, int* d_nkept, int* d_status, int64_t* noconv,
                       int64_t* leadzero, hipStream_t s, const char** kernels);
 
+// LPC spectral envelopes and refined peaks (k_lpcenv.hip; include/pvx.h: pvx_lpc_envelope, pvx_peaks_refine).  Every pointer is
+// device memory; the outputs are each nullable.  *overflow: the first row (from 0) with more than maxpk peaks, *invalid: the first
+// row with a zero leading coefficient / a selected index outside 1 .. npts - 2; -1 otherwise.  Synchronises the stream.
+int pvx_lpcenv_run(const double* d_coef, int64_t n, int order, int npts, double fs, int maxpk, double* d_env, int* d_npk, int* d_idx,
+                   double* d_pos, double* d_val, int64_t* overflow, int64_t* invalid, hipStream_t s, const char** kernels);
+int pvx_peaks_refine_run(const double* d_y, int64_t n, int npts, const double* d_x, int maxpk, const int* d_sel, int* d_npk, int* d_idx,
+                         double* d_pos, double* d_val, int64_t* overflow, int64_t* invalid, hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)

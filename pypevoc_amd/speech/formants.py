@@ -17,7 +17,8 @@ Deviations from the reference:
   * the caller's array is not modified (the reference pre-emphasises it in place);
   * float32 and int16 samples are widened to float64 before the difference (the reference filters float32 in float32 and
     lets int16 wrap);
-  * Formants(full=True) raises NotImplementedError: it needs PeakFinder.refine_all, which is not mirrored;
+  * Formants(full=True) raises NotImplementedError here: it needs PeakFinder.refine_all, and speech/envelope.py's Formants
+    runs it (ENVELOPE.md);
   * a polynomial with a zero leading coefficient is refused (np.roots strips leading zeros)."""
 import ctypes
 
@@ -101,9 +102,11 @@ def _check(rc, what, sing, noconv):
     return _lib.check(rc, what)
 
 
-def _formants_run(x, preemph, down, taps, wind, hop, nfr, order, Fs, want=("nkept", "freq", "bw")):
+def _formants_run(x, preemph, down, taps, wind, hop, nfr, order, Fs, want=("nkept", "freq", "bw"), dev_rows=None):
     """pvx_formants on x (a host array, or a float32 / float64 / int16 1-D signal on the GPU, read in place): a dict of
-    the rows in `want` (nkept int32 [nfr]; freq, bw, re, im [nfr][order]; lpc [nfr][order + 1]) as host arrays."""
+    the rows in `want` (nkept int32 [nfr]; freq, bw, re, im [nfr][order]; lpc [nfr][order + 1]) as host arrays.  dev_rows: a
+    dict whose keys name rows that, for a signal on the GPU, are not copied to the host: it receives their flat device
+    tensors instead (speech/envelope.py reads the lpc rows there).  For a host signal it is left as it is."""
     lib = _lib.load()
     bound = _lib.init()
     ptr, code, n, keep, on_dev = glottal._signal(x)
@@ -126,7 +129,9 @@ def _formants_run(x, preemph, down, taps, wind, hop, nfr, order, Fs, want=("nkep
         rc = lib.pvx_formants_dev(*head, *[ctypes.c_void_p(outs[k].data_ptr()) if k in outs else None for k in names],
                                   ctypes.byref(sing), ctypes.byref(noconv), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         _check(rc, "pvx_formants_dev", sing, noconv)
-        res = {k: outs[k].cpu().numpy()[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in want}
+        stay = dev_rows if dev_rows is not None else {}
+        res = {k: outs[k].cpu().numpy()[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in want if k not in stay}
+        stay.update({k: outs[k] for k in stay if k in outs})
     else:
         res = {k: np.empty(shapes[k], dtype=np.int32 if k == "nkept" else np.float64) for k in want}
         args = [None if k not in res else (res[k].ctypes.data_as(_lib.c_int32_p) if k == "nkept" else _lib.dptr(res[k])) for k in names]
@@ -151,13 +156,14 @@ def Formants(w, Fs, tWind=0.025, tHop=0.0125,
        modelOrder: model order for linear prediction (LPC)
        hpFreq:     > 0 switches the pre-emphasis w[i] - w[i+1] on (its value
                     is not used, as in the reference)
-       full:       not mirrored (NotImplementedError)
+       full:       NotImplementedError here; pypevoc_amd.speech.envelope.Formants runs it
 
        returns Time [frames], Form and BandWidths [frames][int(modelOrd/2)], NaN where a frame has fewer formants
     '''
     if full:
         raise NotImplementedError("Formants(full=True) (pypevoc/speech/SpeechAnalysis.py:298-311) needs PeakFinder.refine_all, "
-                                  "which is not mirrored: see INTEGRATION.md")
+                                  "which this function does not run: pypevoc_amd.speech.envelope.Formants(full=True) does "
+                                  "(see INTEGRATION.md)")
     n = glottal._signal(w)[2]
     down, wLen, FsN, nwind, hop, nFrames, Time = geometry(n, Fs, tWind, tHop, fMax)
     ncols = int(modelOrd / 2)
