@@ -693,6 +693,65 @@ int64_t pvx_peaks_refine_dev(const double* d_y, int64_t n, int npts, const doubl
                              int32_t* d_idx, double* d_pos, double* d_val, int64_t* overflow_row, void* stream);
 const char* pvx_envelope_last_kernels(void);
 
+/* ---- speech segmentation on band energies (pypevoc/speech/SpeechSegmenter.py: process :203-222, the parabolic fit :224-260,
+ *      refine_segment_all_bands :262-302, refine_transition_points :39-124; SEGMENT.md) ----
+ *
+ * All three stages read band energies as pvx_filterbank writes them, spec [frames][nband], take dB = 10 log10(energy)
+ * themselves (no floor: 0 gives -inf, and -inf - -inf a NaN that compares false everywhere) and add in numpy's order, so
+ * a value depends on its own frames alone.  1 <= nband <= PVX_FBANK_MAX_NBAND, else PVX_ERR_UNSUPPORTED and no launch.
+ *
+ * pvx_seg_detect: det[i] = sum_b |dB[i+1][b] - dB[i][b]|, i < nfr - 1 (nullable).  Index 1 <= i <= nfr - 3 is kept iff
+ * det[i-1] < det[i], det[i+1] < det[i] (both strict) and det[i] > thresh.  idx [maxseg]: the kept indices, ascending and
+ * left-packed; fpos [maxseg]: i + lpos of c = det[i], b = (det[i+1] - det[i-1]) / 2, a = (det[i+1] + det[i-1]) / 2 - c,
+ * lpos = -b / 2 / a (each nullable; slots beyond the count are not written).  *count: the full number of kept indices.
+ * Returns the number written, or PVX_ERR_SIZE when count > maxseg (the first maxseg are written).  nfr >= 1 (nfr < 2^31);
+ * nfr = 1 launches nothing.
+ *
+ * pvx_seg_refine: per segment s < nseg and band b, with ranges[s] = {ibef0, ibef1, iaft0, iaft1, iall0, iall1} (host array,
+ * int32, each range [first, last + 1) of rows of spec, the two sides inside iall): valb / vala = np.median of dB over ibef /
+ * iaft (NaN for an empty side or one that holds a NaN); valm = (valb + vala) / 2, or with has_thr min(vala, valb) + thr; the
+ * crossings k, 0 <= k <= len(iall) - 2, with (f[k] - valm) (f[k+1] - valm) < 0 over f = dB[iall]; of them the k nearest to
+ * len(ibef), the lower of two equally near: cross [nseg][nband], -1 for none.  pk = tfine[k + ibef0] sr with tfine[j] =
+ * (j hop + half) / tsr, or tseg[s] (host array) without a crossing; w = |valb - vala|; out[s] = sum_b pk w / sum_b w.
+ * valb, vala [nseg][nband], cross and out are each nullable.  A side longer than PVX_SEG_MAX_SIDE or an iall longer than
+ * 2 PVX_SEG_MAX_SIDE + 1: PVX_ERR_UNSUPPORTED; a range outside 0 .. nfine or a side outside iall: PVX_ERR_INVALID.  Returns
+ * nseg; nseg = 0 launches nothing.
+ *
+ * pvx_seg_transitions: refine_transition_points on nser series of n points, series s at v[s row_stride + k elem_stride];
+ * escale > 0: v holds energies and x = 10 log10(v escale), escale = 0: x = v.  tx: host array of ascending times, [n]
+ * (tx_stride 0) or [nser][n] (tx_stride n); trt: host array [nser].  Per series ttr, vbef, vaft and status:
+ *   PVX_SEG_OUTSIDE      trt outside tx: (trt, 0, 0)
+ *   PVX_SEG_EMPTY_SIDE   no point after trt, or none before it in modes MINMAX and PCT: NaN
+ *   PVX_SEG_NO_CROSSING  vbef and vaft are written, ttr is NaN
+ * mode PVX_SEG_MINMAX / MEDIAN / MEAN / PCT (np.percentile's linear method at pct and 100 - pct, 0 <= pct <= 100).
+ * 1 <= n <= PVX_SEG_MAX_SERIES, else PVX_ERR_UNSUPPORTED.  Returns nser; nser = 0 launches nothing.
+ *
+ * The _dev forms take device memory for the energies and every output (ranges, tseg, tx and trt stay host arrays), work on
+ * `stream` and are synchronised before they return.  pvx_segment_last_kernels: what the calling thread's last call of the
+ * six ran ("k_seg_detect", "k_seg_refine", "k_seg_transitions"; "" when it launched nothing).
+ */
+#define PVX_SEG_MAX_SIDE 256
+#define PVX_SEG_MAX_SERIES 4096
+typedef enum { PVX_SEG_MINMAX = 0, PVX_SEG_MEDIAN = 1, PVX_SEG_MEAN = 2, PVX_SEG_PCT = 3 } pvx_seg_mode;
+typedef enum { PVX_SEG_OK = 0, PVX_SEG_OUTSIDE = 1, PVX_SEG_EMPTY_SIDE = 2, PVX_SEG_NO_CROSSING = 3 } pvx_seg_status;
+int64_t pvx_seg_detect(const double* spec, int64_t nfr, int nband, double thresh, int maxseg, double* det, int32_t* idx, double* fpos,
+                       int64_t* count);
+int64_t pvx_seg_detect_dev(const double* d_spec, int64_t nfr, int nband, double thresh, int maxseg, double* d_det, int32_t* d_idx,
+                           double* d_fpos, int64_t* count, void* stream);
+int64_t pvx_seg_refine(const double* spec, int64_t nfine, int nband, const int32_t* ranges, const double* tseg, int64_t nseg, int hop,
+                       double half, double tsr, double sr, double thr, int has_thr, double* valb, double* vala, int32_t* cross,
+                       double* out);
+int64_t pvx_seg_refine_dev(const double* d_spec, int64_t nfine, int nband, const int32_t* ranges, const double* tseg, int64_t nseg,
+                           int hop, double half, double tsr, double sr, double thr, int has_thr, double* d_valb, double* d_vala,
+                           int32_t* d_cross, double* d_out, void* stream);
+int64_t pvx_seg_transitions(const double* v, int64_t nser, int n, int64_t row_stride, int64_t elem_stride, double escale, const double* tx,
+                            int64_t tx_stride, const double* trt, int mode, double pct, double thr, double* ttr, double* vbef,
+                            double* vaft, int32_t* status);
+int64_t pvx_seg_transitions_dev(const double* d_v, int64_t nser, int n, int64_t row_stride, int64_t elem_stride, double escale,
+                                const double* tx, int64_t tx_stride, const double* trt, int mode, double pct, double thr, double* d_ttr,
+                                double* d_vbef, double* d_vaft, int32_t* d_status, void* stream);
+const char* pvx_segment_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

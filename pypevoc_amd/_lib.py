@@ -190,6 +190,21 @@ SIGNATURES = {
     "pvx_peaks_refine_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] +
                              [ctypes.c_void_p] * 5 + [c_int64_p, ctypes.c_void_p]),
     "pvx_envelope_last_kernels": (ctypes.c_char_p, []),
+    "pvx_seg_detect": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_int32_p,
+                                        c_double_p, c_int64_p]),
+    "pvx_seg_detect_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int] +
+                           [ctypes.c_void_p] * 3 + [c_int64_p, ctypes.c_void_p]),
+    "pvx_seg_refine": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, c_int32_p, c_double_p, ctypes.c_int64, ctypes.c_int] +
+                       [ctypes.c_double] * 4 + [ctypes.c_int, c_double_p, c_double_p, c_int32_p, c_double_p]),
+    "pvx_seg_refine_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_int32_p, c_double_p, ctypes.c_int64, ctypes.c_int] +
+                           [ctypes.c_double] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "pvx_seg_transitions": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, c_double_p,
+                                             ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p,
+                                             c_double_p, c_int32_p]),
+    "pvx_seg_transitions_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                                 c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                                [ctypes.c_void_p] * 5),
+    "pvx_segment_last_kernels": (ctypes.c_char_p, []),
 }
 
 

@@ -3056,6 +3056,162 @@ extern "C" int64_t pvx_peaks_refine_dev(const double* d_y, int64_t n, int npts, 
     return peaks_refine_body<true>(d_y, n, npts, d_x, maxpk, d_sel, d_npk, d_idx, d_pos, d_val, overflow_row, (hipStream_t)stream);
 }
 
+// ---- speech segmentation on band energies (k_segment.hip) ----------------------------------
+static thread_local const char* t_segment_kernels = "";
+extern "C" const char* pvx_segment_last_kernels(void) { return t_segment_kernels; }
+
+static int seg_bands(const char* what, int nband) {
+    if (nband < 1) { pvx_set_error("%s: a table without bands", what); return PVX_ERR_INVALID; }
+    if (nband > PVX_FBANK_MAX_NBAND) { pvx_set_error("%s: %d bands (the kernels take up to %d)", what, nband, PVX_FBANK_MAX_NBAND); return PVX_ERR_UNSUPPORTED; }
+    return PVX_OK;
+}
+
+template <bool DEV>
+static int64_t seg_detect_body(const double* spec, int64_t nfr, int nband, double thresh, int maxseg, double* det, int32_t* idx, double* fpos,
+                               int64_t* count, hipStream_t s) {
+    if (count) *count = 0;
+    int rc;                                                          // (arguments first: the limits answer without a device too)
+    t_segment_kernels = "";
+    if ((rc = seg_bands("pvx_seg_detect", nband)) != PVX_OK) return rc;
+    if (nfr < 1 || nfr > 0x7fffffffLL || maxseg < 0) { pvx_set_error("bad pvx_seg_detect argument (1 <= nfr < 2^31, maxseg >= 0)"); return PVX_ERR_INVALID; }
+    if (!spec) { pvx_set_error("null pvx_seg_detect table"); return PVX_ERR_INVALID; }
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    if (nfr < 2) return 0;
+    const size_t nd = (size_t)nfr - 1, K = (size_t)maxseg;
+    int64_t total = 0;
+    if (DEV) {
+        if ((rc = pvx_seg_detect_run(spec, nfr, nband, thresh, maxseg, det, idx, fpos, &total, s, &t_segment_kernels)) != PVX_OK) return rc;
+    } else {
+        DevMem ds, dd, di, dp;
+        const size_t sb = (size_t)nfr * nband * 8;
+        if ((rc = ds.alloc(sb)) != PVX_OK || (det && (rc = dd.alloc(nd * 8)) != PVX_OK) || (idx && (rc = di.alloc(K * 4)) != PVX_OK) ||
+            (fpos && (rc = dp.alloc(K * 8)) != PVX_OK)) return rc;
+        if ((rc = host_to_device(ds.get(), spec, sb)) != PVX_OK) return rc;
+        if ((rc = pvx_seg_detect_run(ds.as<double>(), nfr, nband, thresh, maxseg, det ? dd.as<double>() : nullptr, idx ? di.as<int>() : nullptr,
+                                     fpos ? dp.as<double>() : nullptr, &total, s, &t_segment_kernels)) != PVX_OK) return rc;
+        const size_t got = (size_t)std::min<int64_t>(total, maxseg);
+        if ((det && (rc = device_to_host(det, dd.get(), nd * 8)) != PVX_OK) || (idx && got && (rc = device_to_host(idx, di.get(), got * 4)) != PVX_OK) ||
+            (fpos && got && (rc = device_to_host(fpos, dp.get(), got * 8)) != PVX_OK)) return rc;
+    }
+    if (count) *count = total;
+    if (total > maxseg && (idx || fpos)) {
+        pvx_set_error("pvx_seg_detect: %lld peaks above the threshold, the lists hold maxseg = %d", (long long)total, maxseg);
+        return PVX_ERR_SIZE;
+    }
+    return std::min<int64_t>(total, maxseg);
+}
+
+extern "C" int64_t pvx_seg_detect(const double* spec, int64_t nfr, int nband, double thresh, int maxseg, double* det, int32_t* idx, double* fpos,
+                                  int64_t* count) {
+    return seg_detect_body<false>(spec, nfr, nband, thresh, maxseg, det, idx, fpos, count, nullptr);
+}
+
+extern "C" int64_t pvx_seg_detect_dev(const double* d_spec, int64_t nfr, int nband, double thresh, int maxseg, double* d_det, int32_t* d_idx,
+                                      double* d_fpos, int64_t* count, void* stream) {
+    return seg_detect_body<true>(d_spec, nfr, nband, thresh, maxseg, d_det, d_idx, d_fpos, count, (hipStream_t)stream);
+}
+
+template <bool DEV>
+static int64_t seg_refine_body(const double* spec, int64_t nfine, int nband, const int32_t* ranges, const double* tseg, int64_t nseg, int hop,
+                               double half, double tsr, double sr, double thr, int has_thr, double* valb, double* vala, int32_t* cross, double* out,
+                               hipStream_t s) {
+    int rc;
+    t_segment_kernels = "";
+    if ((rc = seg_bands("pvx_seg_refine", nband)) != PVX_OK) return rc;
+    if (nfine < 0 || nfine > 0x7fffffffLL || nseg < 0 || hop < 1) { pvx_set_error("bad pvx_seg_refine argument (0 <= nfine < 2^31, nseg >= 0, hop >= 1)"); return PVX_ERR_INVALID; }
+    if (nseg == 0) return 0;
+    if (!ranges || !tseg || (nfine > 0 && !spec)) { pvx_set_error("null pvx_seg_refine table"); return PVX_ERR_INVALID; }
+    for (int64_t i = 0; i < nseg; i++) {
+        const int32_t* r = ranges + i * 6;
+        const bool inside = r[4] >= 0 && r[4] <= r[5] && r[5] <= nfine && r[0] >= r[4] && r[0] <= r[1] && r[1] <= r[5] && r[2] >= r[4] &&
+                            r[2] <= r[3] && r[3] <= r[5];
+        if (!inside) { pvx_set_error("pvx_seg_refine: segment %lld: a range outside 0 .. nfine, or a side outside iall", (long long)i); return PVX_ERR_INVALID; }
+        if (r[1] - r[0] > PVX_SEG_MAX_SIDE || r[3] - r[2] > PVX_SEG_MAX_SIDE || r[5] - r[4] > 2 * PVX_SEG_MAX_SIDE + 1) {
+            pvx_set_error("pvx_seg_refine: segment %lld: a side of more than %d frames (or an iall of more than %d)", (long long)i,
+                          PVX_SEG_MAX_SIDE, 2 * PVX_SEG_MAX_SIDE + 1);
+            return PVX_ERR_UNSUPPORTED;
+        }
+    }
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    if (DEV) {
+        if ((rc = pvx_seg_refine_run(spec, nfine, nband, ranges, tseg, nseg, hop, half, tsr, sr, thr, has_thr, valb, vala, cross, out, s,
+                                     &t_segment_kernels)) != PVX_OK) return rc;
+        return nseg;
+    }
+    DevMem ds, db, da, dc, dout;
+    const size_t sb = (size_t)nfine * nband * 8, cells = (size_t)nseg * nband;
+    if ((rc = ds.alloc(sb)) != PVX_OK || (valb && (rc = db.alloc(cells * 8)) != PVX_OK) || (vala && (rc = da.alloc(cells * 8)) != PVX_OK) ||
+        (cross && (rc = dc.alloc(cells * 4)) != PVX_OK) || (out && (rc = dout.alloc((size_t)nseg * 8)) != PVX_OK)) return rc;
+    if (sb && (rc = host_to_device(ds.get(), spec, sb)) != PVX_OK) return rc;
+    if ((rc = pvx_seg_refine_run(ds.as<double>(), nfine, nband, ranges, tseg, nseg, hop, half, tsr, sr, thr, has_thr, valb ? db.as<double>() : nullptr,
+                                 vala ? da.as<double>() : nullptr, cross ? dc.as<int>() : nullptr, out ? dout.as<double>() : nullptr, s,
+                                 &t_segment_kernels)) != PVX_OK) return rc;
+    if ((valb && (rc = device_to_host(valb, db.get(), cells * 8)) != PVX_OK) || (vala && (rc = device_to_host(vala, da.get(), cells * 8)) != PVX_OK) ||
+        (cross && (rc = device_to_host(cross, dc.get(), cells * 4)) != PVX_OK) || (out && (rc = device_to_host(out, dout.get(), (size_t)nseg * 8)) != PVX_OK)) return rc;
+    return nseg;
+}
+
+extern "C" int64_t pvx_seg_refine(const double* spec, int64_t nfine, int nband, const int32_t* ranges, const double* tseg, int64_t nseg, int hop,
+                                  double half, double tsr, double sr, double thr, int has_thr, double* valb, double* vala, int32_t* cross,
+                                  double* out) {
+    return seg_refine_body<false>(spec, nfine, nband, ranges, tseg, nseg, hop, half, tsr, sr, thr, has_thr, valb, vala, cross, out, nullptr);
+}
+
+extern "C" int64_t pvx_seg_refine_dev(const double* d_spec, int64_t nfine, int nband, const int32_t* ranges, const double* tseg, int64_t nseg,
+                                      int hop, double half, double tsr, double sr, double thr, int has_thr, double* d_valb, double* d_vala,
+                                      int32_t* d_cross, double* d_out, void* stream) {
+    return seg_refine_body<true>(d_spec, nfine, nband, ranges, tseg, nseg, hop, half, tsr, sr, thr, has_thr, d_valb, d_vala, d_cross, d_out,
+                                 (hipStream_t)stream);
+}
+
+template <bool DEV>
+static int64_t seg_transitions_body(const double* v, int64_t nser, int n, int64_t row_stride, int64_t elem_stride, double escale, const double* tx,
+                                    int64_t tx_stride, const double* trt, int mode, double pct, double thr, double* ttr, double* vbef, double* vaft,
+                                    int32_t* status, hipStream_t s) {
+    int rc;
+    t_segment_kernels = "";
+    if (n > PVX_SEG_MAX_SERIES) { pvx_set_error("pvx_seg_transitions: series of %d points (the kernel takes up to %d)", n, PVX_SEG_MAX_SERIES); return PVX_ERR_UNSUPPORTED; }
+    if (nser < 0 || n < 1 || row_stride < 0 || elem_stride < 1 || !(escale >= 0.0) || (tx_stride != 0 && tx_stride != n) || mode < PVX_SEG_MINMAX ||
+        mode > PVX_SEG_PCT || !(pct >= 0.0 && pct <= 100.0)) {
+        pvx_set_error("bad pvx_seg_transitions argument (nser >= 0, n >= 1, strides, escale >= 0, tx_stride 0 or n, a known mode, 0 <= pct <= 100)");
+        return PVX_ERR_INVALID;
+    }
+    if (nser == 0) return 0;
+    if (!v || !tx || !trt || !ttr || !vbef || !vaft || !status) { pvx_set_error("null pvx_seg_transitions array"); return PVX_ERR_INVALID; }
+    for (int64_t r = 0; r < (tx_stride ? nser : 1); r++)
+        for (int k = 0; k + 1 < n; k++)
+            if (!(tx[r * n + k] <= tx[r * n + k + 1])) { pvx_set_error("pvx_seg_transitions: tx must ascend (row %lld, point %d)", (long long)r, k); return PVX_ERR_INVALID; }
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    if (DEV) {
+        if ((rc = pvx_seg_transitions_run(v, nser, n, row_stride, elem_stride, escale, tx, tx_stride, trt, mode, pct, thr, ttr, vbef, vaft, status, s,
+                                          &t_segment_kernels)) != PVX_OK) return rc;
+        return nser;
+    }
+    const size_t span = (size_t)(nser - 1) * row_stride + (size_t)(n - 1) * elem_stride + 1, ob = (size_t)nser * 8;
+    DevMem dv, d1, d2, d3, d4;
+    if ((rc = dv.alloc(span * 8)) != PVX_OK || (rc = d1.alloc(ob)) != PVX_OK || (rc = d2.alloc(ob)) != PVX_OK || (rc = d3.alloc(ob)) != PVX_OK ||
+        (rc = d4.alloc((size_t)nser * 4)) != PVX_OK) return rc;
+    if ((rc = host_to_device(dv.get(), v, span * 8)) != PVX_OK) return rc;
+    if ((rc = pvx_seg_transitions_run(dv.as<double>(), nser, n, row_stride, elem_stride, escale, tx, tx_stride, trt, mode, pct, thr, d1.as<double>(),
+                                      d2.as<double>(), d3.as<double>(), d4.as<int>(), s, &t_segment_kernels)) != PVX_OK) return rc;
+    if ((rc = device_to_host(ttr, d1.get(), ob)) != PVX_OK || (rc = device_to_host(vbef, d2.get(), ob)) != PVX_OK ||
+        (rc = device_to_host(vaft, d3.get(), ob)) != PVX_OK || (rc = device_to_host(status, d4.get(), (size_t)nser * 4)) != PVX_OK) return rc;
+    return nser;
+}
+
+extern "C" int64_t pvx_seg_transitions(const double* v, int64_t nser, int n, int64_t row_stride, int64_t elem_stride, double escale, const double* tx,
+                                       int64_t tx_stride, const double* trt, int mode, double pct, double thr, double* ttr, double* vbef,
+                                       double* vaft, int32_t* status) {
+    return seg_transitions_body<false>(v, nser, n, row_stride, elem_stride, escale, tx, tx_stride, trt, mode, pct, thr, ttr, vbef, vaft, status, nullptr);
+}
+
+extern "C" int64_t pvx_seg_transitions_dev(const double* d_v, int64_t nser, int n, int64_t row_stride, int64_t elem_stride, double escale,
+                                           const double* tx, int64_t tx_stride, const double* trt, int mode, double pct, double thr, double* d_ttr,
+                                           double* d_vbef, double* d_vaft, int32_t* d_status, void* stream) {
+    return seg_transitions_body<true>(d_v, nser, n, row_stride, elem_stride, escale, tx, tx_stride, trt, mode, pct, thr, d_ttr, d_vbef, d_vaft,
+                                      d_status, (hipStream_t)stream);
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

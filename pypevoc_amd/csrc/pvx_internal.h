@@ -407,6 +407,17 @@ int pvx_lpcenv_run(const double* d_coef, int64_t n, int order, int npts, double 
 int pvx_peaks_refine_run(const double* d_y, int64_t n, int npts, const double* d_x, int maxpk, const int* d_sel, int* d_npk, int* d_idx,
                          double* d_pos, double* d_val, int64_t* overflow, int64_t* invalid, hipStream_t s, const char** kernels);
 
+// speech segmentation on device band energies (k_segment.hip; include/pvx.h: pvx_seg_detect, pvx_seg_refine, pvx_seg_transitions).
+// The small tables (ranges, tseg, tx, trt) are host arrays, staged by the call; all three synchronise the stream.
+int pvx_seg_detect_run(const double* d_spec, int64_t nfr, int nband, double thresh, int maxseg, double* d_det, int* d_idx, double* d_fpos,
+                       int64_t* count, hipStream_t s, const char** kernels);
+int pvx_seg_refine_run(const double* d_spec, int64_t nfine, int nband, const int32_t* h_ranges, const double* h_tseg, int64_t nseg, int hop,
+                       double half, double tsr, double sr, double thr, int has_thr, double* d_valb, double* d_vala, int* d_cross,
+                       double* d_out, hipStream_t s, const char** kernels);
+int pvx_seg_transitions_run(const double* d_v, int64_t nser, int n, int64_t row_stride, int64_t elem_stride, double escale,
+                            const double* h_tx, int64_t tx_stride, const double* h_trt, int mode, double pct, double thr, double* d_ttr,
+                            double* d_vbef, double* d_vaft, int* d_status, hipStream_t s, const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)
