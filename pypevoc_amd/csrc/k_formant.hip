@@ -8,7 +8,8 @@
 //   times the window in LDS, pvx_lpc.h's autocorrelation and Levinson recursion, pvx_roots.h on wave 0 over [1, a_1 .. a_p],
 //   then per kept root (imag >= 0, ascending angle) freq = atan2(im, re) Fs / 2 pi and bw = -0.5 (Fs / 2 pi) log |z|.
 //   Rows per frame: nkept, freq / bw [order] (NaN beyond nkept), re / im [order], the LPC row [order + 1]; each nullable.
-// k_polyroots: one wave per polynomial, four per workgroup, rows [n][order + 1]: the same device function.
+// k_polyroots: one wave per polynomial, four per workgroup, rows [n][order + 1]: the same device function on the row divided
+//   by its leading coefficient (the roots' bits do not depend on a power-of-two scale of the row).
 #include <math.h>
 
 #include <map>
@@ -120,11 +121,14 @@ __global__ __launch_bounds__(kThreads) void k_polyroots(RootsParams p) {
     const int64_t row = (int64_t)blockIdx.x * kWaves + wave;
     if (row >= p.n) return;                                          // (a whole wave: nothing below synchronises the workgroup)
     const double* cr = p.coef + row * (P + 1);
-    c[wave][lane] = lane <= P ? cr[lane] : 0.0;
-    if (lane == 0 && P == 64) c[wave][64] = cr[64];
+    // the monic polynomial is iterated: |p'|^2 and the stop test then do not depend on the row's scale (c / 1.0 is c itself,
+    // a power of two changes no significand)
+    const double lead = cr[0];
+    c[wave][lane] = lane <= P ? cr[lane] / lead : 0.0;
+    if (lane == 0 && P == 64) c[wave][64] = cr[64] / lead;
     pvxroots::lds_sync();
     int nk = 0, st = pvxroots::kLeadZero;
-    if (c[wave][0] != 0.0) st = pvxroots::wave_roots(c[wave], P, sre[wave], sim[wave], &nk);   // (wave-uniform)
+    if (lead != 0.0) st = pvxroots::wave_roots(c[wave], P, sre[wave], sim[wave], &nk);         // (wave-uniform)
     if (lane == 0) { p.status[row] = st; if (p.nkept) p.nkept[row] = nk; }
     if (lane < P) {
         const bool ok = st != pvxroots::kLeadZero;

@@ -82,27 +82,36 @@ __device__ inline int wave_roots(const double* c, int p, double* sre, double* si
         }
     }
     // canonical form: every iterate looks for the iterate nearest its conjugate (itself included; the lowest index among
-    // equals).  One that finds itself, or whose choice is not returned, is real.  Two that find each other are a pair: the
-    // member with the larger imaginary part gives both their real part and the size of the imaginary one.
-    int best = lane;
-    double bd = INFINITY;
-    for (int j = 0; j < q; j++) {
-        const double dx = zr - __shfl(zr, j), dy = -zi - __shfl(zi, j);
-        const double m = dx * dx + dy * dy;
-        if (lane < q && m < bd) { bd = m; best = j; }
-    }
-    const int back = __shfl(best, best);
-    const double or_ = __shfl(zr, best), oi = __shfl(zi, best);
-    if (lane < q) {
-        if (best == lane || back != lane) {
+    // equals).  One that finds itself is real.  Two that find each other are a pair: the member with the larger imaginary
+    // part gives both their real part and the size of the imaginary one.  One whose choice is not returned looks again
+    // among those still without a partner, in the next round (wave-uniform votes; the nearest two of a round always find each
+    // other, so a round settles some, and the rounds are bounded as the iteration is: whatever is left then is real).  A
+    // pair's members are an iterate and its mirror image, whose residuals are the same number.
+    bool open = lane < q;
+    for (int round = 0; round < PVX_ROOTS_MAX_ORDER && __any(open); round++) {
+        int best = lane;
+        double bd = INFINITY;
+        for (int j = 0; j < q; j++) {
+            const double dx = zr - __shfl(zr, j), dy = -zi - __shfl(zi, j);
+            const double m = dx * dx + dy * dy;
+            const int oj = __shfl((int)open, j);
+            if (open && oj && m < bd) { bd = m; best = j; }
+        }
+        const int back = __shfl(best, best);
+        const double or_ = __shfl(zr, best), oi = __shfl(zi, best);
+        if (open && best == lane) {
             zi = 0.0;
-        } else {
+            open = false;
+        } else if (open && back == lane) {
             const bool mine = zi > oi || (zi == oi && lane < best);
             const double mi = fabs(mine ? zi : oi);
             zr = mine ? zr : or_;
             zi = mi == 0.0 ? 0.0 : (mine ? mi : -mi);
+            open = false;
         }
-    } else {
+    }
+    if (open) zi = 0.0;
+    if (lane >= q) {
         zr = 0.0;                                                    // lanes q .. p - 1: the exact zero roots
         zi = 0.0;
     }
