@@ -752,6 +752,73 @@ int64_t pvx_seg_transitions_dev(const double* d_v, int64_t nser, int n, int64_t 
                                 double* d_vbef, double* d_vaft, int32_t* d_status, void* stream);
 const char* pvx_segment_last_kernels(void);
 
+/* ---- pitch jumps on rows of tracks (pypevoc/speech/PitchJumps.py: zscore_wind :50-64, linreg_err :67-84, linreg2_err :87-121,
+ *      JumpDetector.detect_jumps :178-207, calc_jump_params :209-242; JUMPS.md) ----
+ *
+ * Every entry point takes `rows` tracks padded to nmax frames, row r holding len[r] of them (0 <= len[r] <= nmax; a row of
+ * length 0 is legal; len NULL: every row holds nmax).  All arrays are float64 / int32; rows * nmax < 2^31.  The number of
+ * launches does not depend on rows, and a row's results do not depend on the other rows.
+ *
+ * pvx_jump_select: m[r][i] = sqrt(sum_k mag[r][i][k]^2), the sum in np.sum's order of a contiguous run of K values (0.0 from
+ * len[r] on); isel[r][i] = m > max_i(m) * mag_threshold (strict; a NaN magnitude makes the maximum NaN and selects nothing);
+ * tsel, fsel [rows][nmax]: the selected (t, f0) pairs in ascending order, left-packed, 0.0 behind them; nsel [rows] their
+ * number; status [rows]: PVX_JUMP_NAN when a magnitude or a selected t / f0 is NaN.  1 <= K <= PVX_JUMP_MAX_K, else
+ * PVX_ERR_UNSUPPORTED.  Returns rows.  pvx_jump_select_resident: the same for the one signal of a plan after
+ * pvx_analyze_resident -- mag and t are read where they are, f0 is the host array [F] that pvx_f0_resident gave, the outputs
+ * are host arrays of F (nsel and status of one) --, so that the (F, K) array does not cross the link.
+ *
+ * pvx_winstat: out[r][i] for i = wleft, wleft + hop, .. < len[r] - wright, 0.0 elsewhere, over the window j in
+ * [i - wleft, i + wright):
+ *   PVX_WIN_ZMEAN    (x[i] - mean) / std, std with ddof 0 and two-pass (zscore_wind, kind 'mean')
+ *   PVX_WIN_ZMEDIAN  (x[i] - median) / (pct75 - pct25), np.percentile's linear rule (kind 'median'); NaN with a NaN in the window
+ *   PVX_WIN_LINREG   (x[i] - line(t[i])) / std(residuals) of the least-squares line over the window (linreg_err)
+ *   PVX_WIN_LINREG2  the pooled-variance two-sample t of the left side's [i - wleft, i) residuals against the right side's
+ *                    [i, i + wright) about the left line (ttl, flag PVX_WIN_USE_L) and of the right against the left about
+ *                    the right line (ttr, PVX_WIN_USE_R): the mean of {ttl, -ttr} as flagged, NaN with neither (linreg2_err)
+ * The line is b = sum((t - tm)(x - xm)) / sum((t - tm)^2), a = xm - b tm.  3 <= wleft <= PVX_JUMP_MAX_SIDE; wright the same,
+ * or 0 for the kinds other than LINREG2; otherwise (wright < 0 too) PVX_ERR_UNSUPPORTED and no launch.  hop >= 1.  Returns rows.
+ *
+ * pvx_jump_pick: index 1 <= i <= len[r] - 2 is an up-jump iff zs[i] > zs[i-1], zs[i] > zs[i+1] (both strict) and zs[i] >
+ * t_threshold, a down-jump iff zs[i] < zs[i-1], zs[i] < zs[i+1] and zs[i] < -t_threshold (a NaN compares false).  idx, dir
+ * [rows][maxjump]: both kinds merged, ascending and left-packed, dir +1 / -1; njump [rows]: the full count.  Per listed jump,
+ * with il = max(0, i - nsl), ir = min(i + nsl, len[r]): intcpts [rows][maxjump][2] the lines over [il, i) and [i + 1, ir) at
+ * t[i]; sumres [rows][maxjump][2] = sqrt(sum(res^2) / (i - il)) and sqrt(sum(res^2) / (ir - i)) (one more than the points on
+ * the right: the reference's divisor); status [rows][maxjump]: PVX_JUMP_SHORT_SIDE when a side has fewer than two points (its
+ * values are NaN; the reference raises), PVX_JUMP_NAN when a value is NaN otherwise.  nsl >= 1.  Returns rows, or
+ * PVX_ERR_SIZE when a row has more than maxjump jumps (*overflow_row says which; the first maxjump are written and fitted).
+ * zs NULL: idx [rows][maxjump] and njump [rows] are the caller's (calc_jump_params on indices set by hand), dir is not
+ * read, and only intcpts, sumres and status are written; an index outside its row gives NaN and PVX_JUMP_SHORT_SIDE.
+ *
+ * Arguments are checked before a device is needed.  The _dev forms take device memory for every array (len too), work on
+ * `stream` and are synchronised before they return.  pvx_jumps_last_kernels: what the calling thread's last call of these
+ * ran ("k_jump_select", "k_winstat", "k_jump_pick"; "" when it launched nothing).
+ */
+#define PVX_JUMP_MAX_SIDE 256
+#define PVX_JUMP_MAX_K 4096
+typedef enum { PVX_WIN_ZMEAN = 0, PVX_WIN_ZMEDIAN = 1, PVX_WIN_LINREG = 2, PVX_WIN_LINREG2 = 3 } pvx_win_kind;
+#define PVX_WIN_USE_L 1
+#define PVX_WIN_USE_R 2
+#define PVX_JUMP_SHORT_SIDE 1
+#define PVX_JUMP_NAN 2
+int64_t pvx_jump_select(const double* mag, const double* f0, const double* t, const int32_t* len, int64_t rows, int nmax, int K,
+                        double mag_threshold, double* m, int32_t* isel, double* tsel, double* fsel, int32_t* nsel, int32_t* status);
+int64_t pvx_jump_select_dev(const double* d_mag, const double* d_f0, const double* d_t, const int32_t* d_len, int64_t rows, int nmax, int K,
+                            double mag_threshold, double* d_m, int32_t* d_isel, double* d_tsel, double* d_fsel, int32_t* d_nsel,
+                            int32_t* d_status, void* stream);
+int64_t pvx_jump_select_resident(pvx_plan* plan, const double* f0, double mag_threshold, double* m, int32_t* isel, double* tsel,
+                                 double* fsel, int32_t* nsel, int32_t* status);
+int64_t pvx_winstat(const double* t, const double* x, const int32_t* len, int64_t rows, int nmax, int kind, int wleft, int wright, int hop,
+                    int flags, double* out);
+int64_t pvx_winstat_dev(const double* d_t, const double* d_x, const int32_t* d_len, int64_t rows, int nmax, int kind, int wleft, int wright,
+                        int hop, int flags, double* d_out, void* stream);
+int64_t pvx_jump_pick(const double* zs, const double* t, const double* x, const int32_t* len, int64_t rows, int nmax, double t_threshold,
+                      int nsl, int maxjump, int32_t* idx, int32_t* dir, int32_t* njump, double* intcpts, double* sumres, int32_t* status,
+                      int64_t* overflow_row);
+int64_t pvx_jump_pick_dev(const double* d_zs, const double* d_t, const double* d_x, const int32_t* d_len, int64_t rows, int nmax,
+                          double t_threshold, int nsl, int maxjump, int32_t* d_idx, int32_t* d_dir, int32_t* d_njump, double* d_intcpts,
+                          double* d_sumres, int32_t* d_status, int64_t* overflow_row, void* stream);
+const char* pvx_jumps_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

@@ -205,6 +205,19 @@ SIGNATURES = {
                                                  c_double_p, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
                                 [ctypes.c_void_p] * 5),
     "pvx_segment_last_kernels": (ctypes.c_char_p, []),
+    "pvx_jump_select": (ctypes.c_int64, [c_double_p, c_double_p, c_double_p, c_int32_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                         c_double_p, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "pvx_jump_select_dev": (ctypes.c_int64, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double] +
+                            [ctypes.c_void_p] * 7),
+    "pvx_jump_select_resident": (ctypes.c_int64, [ctypes.c_void_p, c_double_p, ctypes.c_double, c_double_p, c_int32_p, c_double_p, c_double_p,
+                                                  c_int32_p, c_int32_p]),
+    "pvx_winstat": (ctypes.c_int64, [c_double_p, c_double_p, c_int32_p, ctypes.c_int64] + [ctypes.c_int] * 6 + [c_double_p]),
+    "pvx_winstat_dev": (ctypes.c_int64, [ctypes.c_void_p] * 3 + [ctypes.c_int64] + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_void_p]),
+    "pvx_jump_pick": (ctypes.c_int64, [c_double_p, c_double_p, c_double_p, c_int32_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                       ctypes.c_int, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int64_p]),
+    "pvx_jump_pick_dev": (ctypes.c_int64, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int] +
+                          [ctypes.c_void_p] * 6 + [c_int64_p, ctypes.c_void_p]),
+    "pvx_jumps_last_kernels": (ctypes.c_char_p, []),
 }
 
 

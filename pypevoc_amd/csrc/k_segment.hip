@@ -34,55 +34,7 @@
 namespace {
 
 using namespace pvxsel;
-
-// ---- np.sum's order -----------------------------------------------------------------------------------------------------
-// numpy adds a contiguous float64 run of n < 8 values one by one from 0.0; 8 <= n <= 128 into eight accumulators by index % 8
-// up to n - n % 8, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the rest one by one; a longer run as the sum of its
-// two halves, the first of n / 2 rounded down to a multiple of 8.  np.sum and np.mean start from 0.0 + that.
-template <class F> __device__ __forceinline__ double np_block_sum(F a, int lo, int n) {   // n <= 128
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; i++) res += a(lo + i);
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = a(lo + j);
-    const int n8 = n - n % 8;
-    for (int i = 8; i < n8; i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) r[j] += a(lo + i + j);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (int i = n8; i < n; i++) res += a(lo + i);
-    return res;
-}
-
-// the recursion over halves as a post-order walk with an explicit stack: a run longer than 128 becomes (join, right half, left
-// half); the blocks' sums come in index order and a join adds the two sums below it, left + right
-template <class F> __device__ __forceinline__ double np_sum(F a, int n) {
-    struct Item { int lo, n, join; };
-    Item todo[24];                                                   // PVX_SEG_MAX_SERIES: five levels, two items a level
-    double sums[8];
-    int nt = 0, ns = 0;
-    todo[nt++] = {0, n, 0};
-    while (nt > 0) {
-        const Item s = todo[--nt];
-        if (s.join) {
-            const double right = sums[--ns], left = sums[--ns];
-            sums[ns++] = left + right;
-        } else if (s.n <= 128) {
-            sums[ns++] = np_block_sum(a, s.lo, s.n);
-        } else {
-            int n2 = s.n / 2;
-            n2 -= n2 % 8;
-            todo[nt++] = {0, 0, 1};
-            todo[nt++] = {s.lo + n2, s.n - n2, 0};
-            todo[nt++] = {s.lo, n2, 0};
-        }
-    }
-    return 0.0 + sums[0];
-}
+static_assert(PVX_SEG_MAX_SERIES <= kNpSumMaxRun, "np_sum's stacks (pvx_select.h) are sized for runs of up to kNpSumMaxRun terms");
 
 // ---- k_seg_detect -------------------------------------------------------------------------------------------------------
 constexpr int kDetTile = 512, kDetChunk = 8, kDetWaves = kDetTile / 64;
@@ -271,23 +223,6 @@ struct TransParams {
     double *ttr, *vbef, *vaft;  // [nser]
     int* status;                // [nser]
 };
-
-// np.percentile(side, q100), method 'linear', from the sorted side's places: which two places it reads (plan), and its value
-struct PctPlan { int prev, next; double t; };
-__device__ __forceinline__ PctPlan pct_plan(int m, double q100) {
-    const double q = q100 / 100.0;
-    const double virt = (double)m * q + (1.0 + q * (1.0 - 1.0 - 1.0)) - 1.0;
-    double prev = floor(virt), next = prev + 1.0, gprev = prev;
-    if (virt >= (double)(m - 1)) { prev = next = (double)(m - 1); gprev = -1.0; }   // numpy writes -1 (the last) and keeps it for gamma
-    if (virt < 0.0) { prev = next = 0.0; gprev = 0.0; }
-    PctPlan pl;
-    pl.prev = (int)prev; pl.next = (int)next; pl.t = virt - gprev;
-    return pl;
-}
-__device__ __forceinline__ double pct_value(double a, double b, double t) {
-    const double diff = b - a;
-    return t >= 0.5 ? b - diff * (1.0 - t) : a + diff * t;
-}
 
 __global__ __launch_bounds__(64) void k_seg_transitions(TransParams p) {
     __shared__ double x[PVX_SEG_MAX_SERIES];

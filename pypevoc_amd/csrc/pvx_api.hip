@@ -3212,6 +3212,229 @@ extern "C" int64_t pvx_seg_transitions_dev(const double* d_v, int64_t nser, int 
                                       d_status, (hipStream_t)stream);
 }
 
+// ---- pitch jumps on rows of tracks (k_jumps.hip) --------------------------------------------
+static thread_local const char* t_jumps_kernels = "";
+extern "C" const char* pvx_jumps_last_kernels(void) { return t_jumps_kernels; }
+
+// rows, nmax and (host form) the lengths of a call: PVX_OK, or the status to return
+static int jump_rows(const char* what, int64_t rows, int nmax, const int32_t* host_len) {
+    if (rows < 0 || rows > 0x7fffffffLL || nmax < 0 || rows * (int64_t)nmax > 0x7fffffffLL) {   // (rows first: the product cannot overflow)
+        pvx_set_error("bad %s argument (0 <= rows < 2^31, nmax >= 0, rows * nmax < 2^31)", what);
+        return PVX_ERR_INVALID;
+    }
+    if (host_len)
+        for (int64_t r = 0; r < rows; r++)
+            if (host_len[r] < 0 || host_len[r] > nmax) { pvx_set_error("%s: row %lld holds %d frames of nmax = %d", what, (long long)r, host_len[r], nmax); return PVX_ERR_INVALID; }
+    return PVX_OK;
+}
+
+// a host array on the device for the length of a call (nullptr stays nullptr)
+struct Staged {
+    DevMem mem;
+    int put(const void* host, size_t bytes) {
+        int rc;
+        if (!host) return PVX_OK;
+        if ((rc = mem.alloc(bytes ? bytes : 8)) != PVX_OK) return rc;
+        return bytes ? host_to_device(mem.get(), host, bytes) : PVX_OK;
+    }
+    int room(size_t bytes) { return mem.alloc(bytes ? bytes : 8); }
+    int get(void* host, size_t bytes) { return bytes ? device_to_host(host, mem.get(), bytes) : PVX_OK; }
+};
+
+// rows without a frame: the per-row counts (and status) are 0 and nothing is launched; returns rows
+template <bool DEV>
+static int64_t jump_zero_counts(int32_t* count, int32_t* status, int64_t rows, hipStream_t s) {
+    const size_t bytes = (size_t)rows * 4;
+    if (DEV) {
+        int rc;
+        if ((rc = pvx_require_device()) != PVX_OK) return rc;
+        PVX_HIP_CHECK(hipMemsetAsync(count, 0, bytes, s));
+        if (status) PVX_HIP_CHECK(hipMemsetAsync(status, 0, bytes, s));
+        PVX_HIP_CHECK(hipStreamSynchronize(s));
+    } else {
+        memset(count, 0, bytes);
+        if (status) memset(status, 0, bytes);
+    }
+    return rows;
+}
+
+template <bool DEV>
+static int64_t jump_select_body(const double* mag, const double* f0, const double* t, const int32_t* len, int64_t rows, int nmax, int K, double thr,
+                                double* m, int32_t* isel, double* tsel, double* fsel, int32_t* nsel, int32_t* status, hipStream_t s) {
+    int rc;
+    t_jumps_kernels = "";
+    if (K > PVX_JUMP_MAX_K) { pvx_set_error("pvx_jump_select: %d peaks per frame (the kernel takes up to %d)", K, PVX_JUMP_MAX_K); return PVX_ERR_UNSUPPORTED; }
+    if (K < 1) { pvx_set_error("bad pvx_jump_select argument (K >= 1)"); return PVX_ERR_INVALID; }
+    if ((rc = jump_rows("pvx_jump_select", rows, nmax, DEV ? nullptr : len)) != PVX_OK) return rc;
+    if (rows == 0) return 0;
+    if (!nsel || !status || (nmax > 0 && (!mag || !f0 || !t || !m || !isel || !tsel || !fsel))) { pvx_set_error("null pvx_jump_select array"); return PVX_ERR_INVALID; }
+    if (nmax == 0) return jump_zero_counts<DEV>(nsel, status, rows, s);   // no frame: nothing selected, no launch (as pvx_winstat)
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    if (DEV) {
+        if ((rc = pvx_jump_select_run(mag, f0, t, len, rows, nmax, K, thr, m, isel, tsel, fsel, nsel, status, s, &t_jumps_kernels)) != PVX_OK) return rc;
+        return rows;
+    }
+    const size_t cells = (size_t)rows * nmax;
+    Staged dmag, df0, dt, dlen, dm, di, dts, dfs, dn, dst;
+    if ((rc = dmag.put(mag, cells * K * 8)) != PVX_OK || (rc = df0.put(f0, cells * 8)) != PVX_OK || (rc = dt.put(t, cells * 8)) != PVX_OK ||
+        (rc = dlen.put(len, (size_t)rows * 4)) != PVX_OK || (rc = dm.room(cells * 8)) != PVX_OK || (rc = di.room(cells * 4)) != PVX_OK ||
+        (rc = dts.room(cells * 8)) != PVX_OK || (rc = dfs.room(cells * 8)) != PVX_OK || (rc = dn.room((size_t)rows * 4)) != PVX_OK ||
+        (rc = dst.room((size_t)rows * 4)) != PVX_OK) return rc;
+    if ((rc = pvx_jump_select_run(dmag.mem.as<double>(), df0.mem.as<double>(), dt.mem.as<double>(), len ? dlen.mem.as<int>() : nullptr, rows, nmax, K, thr,
+                                  dm.mem.as<double>(), di.mem.as<int>(), dts.mem.as<double>(), dfs.mem.as<double>(), dn.mem.as<int>(), dst.mem.as<int>(),
+                                  s, &t_jumps_kernels)) != PVX_OK) return rc;
+    if ((rc = dm.get(m, cells * 8)) != PVX_OK || (rc = di.get(isel, cells * 4)) != PVX_OK || (rc = dts.get(tsel, cells * 8)) != PVX_OK ||
+        (rc = dfs.get(fsel, cells * 8)) != PVX_OK || (rc = dn.get(nsel, (size_t)rows * 4)) != PVX_OK || (rc = dst.get(status, (size_t)rows * 4)) != PVX_OK) return rc;
+    return rows;
+}
+
+extern "C" int64_t pvx_jump_select(const double* mag, const double* f0, const double* t, const int32_t* len, int64_t rows, int nmax, int K,
+                                   double mag_threshold, double* m, int32_t* isel, double* tsel, double* fsel, int32_t* nsel, int32_t* status) {
+    return jump_select_body<false>(mag, f0, t, len, rows, nmax, K, mag_threshold, m, isel, tsel, fsel, nsel, status, nullptr);
+}
+
+extern "C" int64_t pvx_jump_select_dev(const double* d_mag, const double* d_f0, const double* d_t, const int32_t* d_len, int64_t rows, int nmax, int K,
+                                       double mag_threshold, double* d_m, int32_t* d_isel, double* d_tsel, double* d_fsel, int32_t* d_nsel,
+                                       int32_t* d_status, void* stream) {
+    return jump_select_body<true>(d_mag, d_f0, d_t, d_len, rows, nmax, K, mag_threshold, d_m, d_isel, d_tsel, d_fsel, d_nsel, d_status,
+                                  (hipStream_t)stream);
+}
+
+// the selection on a plan's resident mag and t (one signal): f0 goes up, five F-sized arrays come back
+extern "C" int64_t pvx_jump_select_resident(pvx_plan* p, const double* f0, double mag_threshold, double* m, int32_t* isel, double* tsel,
+                                            double* fsel, int32_t* nsel, int32_t* status) {
+    t_jumps_kernels = "";
+    int rc = need_resident(p);
+    if (rc != PVX_OK) return rc;
+    if (p->res_nsig != 1) { pvx_set_error("pvx_jump_select_resident works on one signal (resident results hold %lld)", (long long)p->res_nsig); return PVX_ERR_INVALID; }
+    if (!f0 || !m || !isel || !tsel || !fsel || !nsel || !status) { pvx_set_error("null pvx_jump_select_resident array"); return PVX_ERR_INVALID; }
+    if (p->npks > PVX_JUMP_MAX_K) { pvx_set_error("pvx_jump_select_resident: %d peaks per frame (the kernel takes up to %d)", p->npks, PVX_JUMP_MAX_K); return PVX_ERR_UNSUPPORTED; }
+    const int64_t F = p->res_F;
+    if (F > 0x7fffffffLL) { pvx_set_error("pvx_jump_select_resident: %lld frames", (long long)F); return PVX_ERR_UNSUPPORTED; }
+    const size_t n = (size_t)F;
+    if ((rc = p->d_desc.grow(n * 36 + 16, Sizing::headroom)) != PVX_OK) return rc;
+    const HostOut all = block_ptrs(p->d_res.as<double>(), F, p->npks);
+    double* d_f0 = p->d_desc.as<double>();                           // f0 | m | tsel | fsel | isel | nsel, status
+    double *d_m = d_f0 + n, *d_ts = d_m + n, *d_fs = d_ts + n;
+    int32_t* d_is = (int32_t*)(d_fs + n);
+    int32_t* d_ns = d_is + n;
+    PVX_HIP_CHECK(hipMemcpyAsync(d_f0, f0, n * 8, hipMemcpyHostToDevice, p->s_host));
+    if ((rc = pvx_jump_select_run(all.mag, d_f0, all.t, nullptr, 1, (int)F, p->npks, mag_threshold, d_m, d_is, d_ts, d_fs, d_ns, d_ns + 1, p->s_host,
+                                  &t_jumps_kernels)) != PVX_OK) return rc;
+    int32_t tail[2];
+    if ((rc = device_to_host(m, d_m, n * 8)) != PVX_OK || (rc = device_to_host(isel, d_is, n * 4)) != PVX_OK ||
+        (rc = device_to_host(tsel, d_ts, n * 8)) != PVX_OK || (rc = device_to_host(fsel, d_fs, n * 8)) != PVX_OK ||
+        (rc = device_to_host(tail, d_ns, 8)) != PVX_OK) return rc;
+    *nsel = tail[0];
+    *status = tail[1];
+    return 1;
+}
+
+template <bool DEV>
+static int64_t winstat_body(const double* t, const double* x, const int32_t* len, int64_t rows, int nmax, int kind, int wl, int wr, int hop, int flags,
+                            double* out, hipStream_t s) {
+    int rc;
+    t_jumps_kernels = "";
+    if (kind < PVX_WIN_ZMEAN || kind > PVX_WIN_LINREG2 || hop < 1 || (flags & ~(PVX_WIN_USE_L | PVX_WIN_USE_R))) {
+        pvx_set_error("bad pvx_winstat argument (a known kind, hop >= 1, flags of PVX_WIN_USE_L | PVX_WIN_USE_R)");
+        return PVX_ERR_INVALID;
+    }
+    const bool right_ok = (wr >= 3 && wr <= PVX_JUMP_MAX_SIDE) || (wr == 0 && kind != PVX_WIN_LINREG2);
+    if (wl < 3 || wl > PVX_JUMP_MAX_SIDE || !right_ok) {
+        pvx_set_error("pvx_winstat: window sides %d and %d (the kernel takes 3 .. %d points a side; wright 0 for the kinds other than LINREG2)", wl, wr,
+                      PVX_JUMP_MAX_SIDE);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    if ((rc = jump_rows("pvx_winstat", rows, nmax, DEV ? nullptr : len)) != PVX_OK) return rc;
+    if (rows == 0 || nmax == 0) return rows;
+    if (!t || !x || !out) { pvx_set_error("null pvx_winstat array"); return PVX_ERR_INVALID; }
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    if (DEV) {
+        if ((rc = pvx_winstat_run(t, x, len, rows, nmax, kind, wl, wr, hop, flags, out, s, &t_jumps_kernels)) != PVX_OK) return rc;
+        return rows;
+    }
+    const size_t cells = (size_t)rows * nmax;
+    Staged dt, dx, dlen, dout;
+    if ((rc = dt.put(t, cells * 8)) != PVX_OK || (rc = dx.put(x, cells * 8)) != PVX_OK || (rc = dlen.put(len, (size_t)rows * 4)) != PVX_OK ||
+        (rc = dout.room(cells * 8)) != PVX_OK) return rc;
+    if ((rc = pvx_winstat_run(dt.mem.as<double>(), dx.mem.as<double>(), len ? dlen.mem.as<int>() : nullptr, rows, nmax, kind, wl, wr, hop, flags,
+                              dout.mem.as<double>(), s, &t_jumps_kernels)) != PVX_OK) return rc;
+    if ((rc = dout.get(out, cells * 8)) != PVX_OK) return rc;
+    return rows;
+}
+
+extern "C" int64_t pvx_winstat(const double* t, const double* x, const int32_t* len, int64_t rows, int nmax, int kind, int wleft, int wright, int hop,
+                               int flags, double* out) {
+    return winstat_body<false>(t, x, len, rows, nmax, kind, wleft, wright, hop, flags, out, nullptr);
+}
+
+extern "C" int64_t pvx_winstat_dev(const double* d_t, const double* d_x, const int32_t* d_len, int64_t rows, int nmax, int kind, int wleft, int wright,
+                                   int hop, int flags, double* d_out, void* stream) {
+    return winstat_body<true>(d_t, d_x, d_len, rows, nmax, kind, wleft, wright, hop, flags, d_out, (hipStream_t)stream);
+}
+
+template <bool DEV>
+static int64_t jump_pick_body(const double* zs, const double* t, const double* x, const int32_t* len, int64_t rows, int nmax, double thr, int nsl,
+                              int maxjump, int32_t* idx, int32_t* dir, int32_t* njump, double* intcpts, double* sumres, int32_t* status,
+                              int64_t* overflow_row, hipStream_t s) {
+    int rc;
+    t_jumps_kernels = "";
+    if (overflow_row) *overflow_row = -1;
+    if (nsl < 1 || maxjump < 0 || rows * (int64_t)maxjump > 0x3fffffffLL) {
+        pvx_set_error("bad pvx_jump_pick argument (nsl >= 1, maxjump >= 0, rows * maxjump < 2^30)");
+        return PVX_ERR_INVALID;
+    }
+    if ((rc = jump_rows("pvx_jump_pick", rows, nmax, DEV ? nullptr : len)) != PVX_OK) return rc;
+    if (rows == 0) return 0;
+    if (!njump || (nmax > 0 && (!t || !x)) || (maxjump > 0 && (!idx || !intcpts || !sumres || !status)) || (zs && maxjump > 0 && !dir)) {
+        pvx_set_error("null pvx_jump_pick array");
+        return PVX_ERR_INVALID;
+    }
+    if (nmax == 0) return zs ? jump_zero_counts<DEV>(njump, nullptr, rows, s) : rows;   // no frame: no jump, no launch (lists of the caller's: nothing to fit)
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    const size_t cells = (size_t)rows * nmax, slots = (size_t)rows * maxjump;
+    std::vector<int32_t> counts;
+    const int32_t* got = njump;
+    if (DEV) {
+        if ((rc = pvx_jump_pick_run(zs, t, x, len, rows, nmax, thr, nsl, maxjump, idx, dir, njump, intcpts, sumres, status, s, &t_jumps_kernels)) != PVX_OK) return rc;
+        counts.resize((size_t)rows);
+        if ((rc = device_to_host(counts.data(), njump, (size_t)rows * 4)) != PVX_OK) return rc;
+        got = counts.data();
+    } else {
+        Staged dz, dt, dx, dlen, di, dd, dn, dic, dsr, dst;
+        if ((rc = dz.put(zs, cells * 8)) != PVX_OK || (rc = dt.put(t, cells * 8)) != PVX_OK || (rc = dx.put(x, cells * 8)) != PVX_OK ||
+            (rc = dlen.put(len, (size_t)rows * 4)) != PVX_OK || (rc = zs ? di.room(slots * 4) : di.put(idx, slots * 4)) != PVX_OK ||
+            (rc = dd.room(slots * 4)) != PVX_OK || (rc = zs ? dn.room((size_t)rows * 4) : dn.put(njump, (size_t)rows * 4)) != PVX_OK || (rc = dic.room(slots * 16)) != PVX_OK || (rc = dsr.room(slots * 16)) != PVX_OK ||
+            (rc = dst.room(slots * 4)) != PVX_OK) return rc;
+        if ((rc = pvx_jump_pick_run(zs ? dz.mem.as<double>() : nullptr, dt.mem.as<double>(), dx.mem.as<double>(), len ? dlen.mem.as<int>() : nullptr, rows, nmax, thr, nsl,
+                                    maxjump, di.mem.as<int>(), dd.mem.as<int>(), dn.mem.as<int>(), dic.mem.as<double>(), dsr.mem.as<double>(),
+                                    dst.mem.as<int>(), s, &t_jumps_kernels)) != PVX_OK) return rc;
+        // (slots beyond a row's count hold nothing: the caller reads njump[r] of them)
+        if ((zs && ((rc = dn.get(njump, (size_t)rows * 4)) != PVX_OK || (rc = di.get(idx, slots * 4)) != PVX_OK || (rc = dd.get(dir, slots * 4)) != PVX_OK)) ||
+            (rc = dic.get(intcpts, slots * 16)) != PVX_OK || (rc = dsr.get(sumres, slots * 16)) != PVX_OK || (rc = dst.get(status, slots * 4)) != PVX_OK) return rc;
+    }
+    for (int64_t r = 0; r < rows; r++)
+        if (got[r] > maxjump) {
+            if (overflow_row) *overflow_row = r;
+            pvx_set_error("pvx_jump_pick: row %lld has %d jumps, the lists hold maxjump = %d", (long long)r, got[r], maxjump);
+            return PVX_ERR_SIZE;
+        }
+    return rows;
+}
+
+extern "C" int64_t pvx_jump_pick(const double* zs, const double* t, const double* x, const int32_t* len, int64_t rows, int nmax, double t_threshold,
+                                 int nsl, int maxjump, int32_t* idx, int32_t* dir, int32_t* njump, double* intcpts, double* sumres, int32_t* status,
+                                 int64_t* overflow_row) {
+    return jump_pick_body<false>(zs, t, x, len, rows, nmax, t_threshold, nsl, maxjump, idx, dir, njump, intcpts, sumres, status, overflow_row, nullptr);
+}
+
+extern "C" int64_t pvx_jump_pick_dev(const double* d_zs, const double* d_t, const double* d_x, const int32_t* d_len, int64_t rows, int nmax,
+                                     double t_threshold, int nsl, int maxjump, int32_t* d_idx, int32_t* d_dir, int32_t* d_njump, double* d_intcpts,
+                                     double* d_sumres, int32_t* d_status, int64_t* overflow_row, void* stream) {
+    return jump_pick_body<true>(d_zs, d_t, d_x, d_len, rows, nmax, t_threshold, nsl, maxjump, d_idx, d_dir, d_njump, d_intcpts, d_sumres, d_status,
+                                overflow_row, (hipStream_t)stream);
+}
+
 // ---- result wire format for the multi-GPU gather (k_wire.hip) -------------------------------
 extern "C" int pvx_plan_set_wire_format(pvx_plan* plan, int format) {
     if (!plan) { pvx_set_error("null plan"); return PVX_ERR_INVALID; }

@@ -418,6 +418,17 @@ int pvx_seg_transitions_run(const double* d_v, int64_t nser, int n, int64_t row_
                             const double* h_tx, int64_t tx_stride, const double* h_trt, int mode, double pct, double thr, double* d_ttr,
                             double* d_vbef, double* d_vaft, int* d_status, hipStream_t s, const char** kernels);
 
+// pitch jumps on device rows (k_jumps.hip; include/pvx.h: pvx_jump_select, pvx_winstat, pvx_jump_pick).  Every pointer is device
+// memory and no output is nullable (d_len may be null: every row holds nmax); all three synchronise the stream.
+int pvx_jump_select_run(const double* d_mag, const double* d_f0, const double* d_t, const int* d_len, int64_t rows, int nmax, int K, double thr,
+                        double* d_m, int* d_isel, double* d_tsel, double* d_fsel, int* d_nsel, int* d_status, hipStream_t s,
+                        const char** kernels);
+int pvx_winstat_run(const double* d_t, const double* d_x, const int* d_len, int64_t rows, int nmax, int kind, int wl, int wr, int hop, int flags,
+                    double* d_out, hipStream_t s, const char** kernels);
+int pvx_jump_pick_run(const double* d_zs, const double* d_t, const double* d_x, const int* d_len, int64_t rows, int nmax, double thr, int nsl,
+                      int maxjump, int* d_idx, int* d_dir, int* d_njump, double* d_intcpts, double* d_sumres, int* d_status, hipStream_t s,
+                      const char** kernels);
+
 // result wire format for the multi-GPU gather (k_wire.hip)
 struct WireParams {
     int64_t rows;                     // frames (all signals of the shard)

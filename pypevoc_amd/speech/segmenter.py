@@ -13,7 +13,7 @@ per call, where the reference computes it once per segment.
 Deviations from the reference (SEGMENT.md has the list): the constructor copies the band list instead of appending
 sr/2 to the caller's (and so to its own shared default); mode 'pctYY' reads YY with float(), where the reference's
 np.float raises AttributeError on numpy >= 1.24; a transition without a point after trt raises ValueError, not
-IndexError; SyllableSegmenter, SilenceDetector and MultiChannelSegmenter are not mirrored."""
+IndexError; SyllableSegmenter and MultiChannelSegmenter are not mirrored (SilenceDetector: speech.chunker)."""
 import ctypes
 
 import numpy as np
