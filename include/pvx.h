@@ -819,6 +819,57 @@ int64_t pvx_jump_pick_dev(const double* d_zs, const double* d_t, const double* d
                           double* d_sumres, int32_t* d_status, int64_t* overflow_row, void* stream);
 const char* pvx_jumps_last_kernels(void);
 
+/* ---- fricative descriptors of many snippets of one signal (pypevoc/speech/SpeechAnalysis.py: FricativeDataFromSnip
+ *      :349-384; FRICATIVES.md) ----
+ *
+ * Snippet r = 0 .. nrows - 1 is x[starts[r] : starts[r] + L], one L per call; starts is a host array in every form, in any
+ * order, overlaps allowed.  With nper = min(nwind, L), nov = nper/2, step = nper - nov and nseg = (L - nov)/step (scipy's
+ * count), segment s is the nper samples from starts[r] + s*step and, for the bins k = 0 .. nper/2,
+ *   X_s = rfft((seg_s - mean(seg_s)) * win)       the mean subtracted in the time domain, before the window
+ *   psd[r][k] = c[k] (1/nseg) sum_s |X_s[k]|^2 / (sr sum(win^2))       [nrows][nper/2 + 1]
+ * c[k] = 2, but 1 at k = 0 and, for even nper, at the last bin: scipy.signal.welch(x, fs=sr, nperseg=nwind) with its
+ * defaults.  win: host array [nper], NULL for the periodic Hann window.  x: float32, float64 or int16 samples (pvx_dtype),
+ * widened on load; all arithmetic float64.
+ *
+ * The descriptors of a row (S, freq) of nb >= 2 bins, desc[r] = f_max, slope_left, slope_right, cent, stdev, skew, kurt:
+ * with y = 10 log10 S and imax = argmax S (first index on ties), f_max is freq interpolated at the three-point refinement
+ * of y around max(imax, 1) (the bin itself unless it is a strict maximum of its neighbours; freq[nb-1] at the last bin),
+ * the slopes are 1000 x the least-squares slopes of y over freq on the bins 0 .. imax and imax .. nb-1 (centred sums),
+ * the last four are the centre, standard deviation, skewness and excess kurtosis of the distribution S over freq.  freq is
+ * a host array [nb] in every form (the caller's np.fft.rfftfreq).  status[r]: PVX_FRIC_END_PEAK when imax is 0 or nb-1 (the
+ * fit over one point is NaN), PVX_FRIC_BAD_BIN when a bin is zero, negative or not finite (every output that reads that
+ * bin's logarithm is NaN; a row whose sum is zero is NaN throughout).  Nothing is clamped.  rms[r]: the population standard
+ * deviation of all L samples of the snippet.
+ *
+ * pvx_welch writes psd, pvx_fric_desc the descriptors of given psd rows, pvx_fricative both and rms in one call (psd may be
+ * NULL there).  A row is one wave's work with a fixed summation order: its values do not depend on the grid, on the other
+ * rows of the call, on their order or on where the samples came from, and pvx_fric_desc on the psd rows of pvx_fricative
+ * returns that call's descriptors bit for bit.  nper 512 / 1024 / 2048 run one fused kernel for the spectra, any other
+ * nper a framing kernel + rocFFT + an accumulation kernel per batch of whole snippets; PVX_FRIC_ROWS in the environment
+ * sends every nper down the rows route.  A host call copies the span of samples its rows cover; when that exceeds
+ * PVX_MAX_DEVICE_BYTES it runs groups of consecutive rows (at least one), each with its own span.  PVX_ERR_SIZE for a
+ * snippet that leaves the n samples (the message names the row), L < 2, nrows < 0 or nb < 2; nrows = 0 returns 0 and
+ * launches nothing.  The _dev forms take device memory for the samples and every output, work on `stream` and are
+ * synchronised before they return.  All return nrows or a negative status; calls share the filter banks' per-device
+ * workspace and take turns on it.  pvx_fric_last_kernels: what the calling thread's last call ran
+ * ("k_fric_fused<1024>+k_fric_desc+k_fric_rms", "k_fric_frames+rocfft+k_fric_acc", "k_fric_desc"; "" when it had no row).
+ */
+#define PVX_FRIC_END_PEAK 1
+#define PVX_FRIC_BAD_BIN 2
+int64_t pvx_welch(const void* x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, const double* win,
+                  double sr, double* psd);
+int64_t pvx_welch_dev(const void* d_x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, const double* win,
+                      double sr, double* d_psd, void* stream);
+int64_t pvx_fric_desc(const double* psd, int64_t nrows, int nb, const double* freq, double* desc, int32_t* imax, int32_t* status);
+int64_t pvx_fric_desc_dev(const double* d_psd, int64_t nrows, int nb, const double* freq, double* d_desc, int32_t* d_imax,
+                          int32_t* d_status, void* stream);
+int64_t pvx_fricative(const void* x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, const double* win,
+                      double sr, const double* freq, double* psd, double* desc, int32_t* imax, int32_t* status, double* rms);
+int64_t pvx_fricative_dev(const void* d_x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind,
+                          const double* win, double sr, const double* freq, double* d_psd, double* d_desc, int32_t* d_imax,
+                          int32_t* d_status, double* d_rms, void* stream);
+const char* pvx_fric_last_kernels(void);
+
 /* ---- multi-GPU result gather: compact wire format --------------------------------------
  *
  * The reference has no multi-device path; its results are the five float64 [F, K] arrays of

@@ -218,6 +218,17 @@ SIGNATURES = {
     "pvx_jump_pick_dev": (ctypes.c_int64, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int] +
                           [ctypes.c_void_p] * 6 + [c_int64_p, ctypes.c_void_p]),
     "pvx_jumps_last_kernels": (ctypes.c_char_p, []),
+    "pvx_welch": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p,
+                                   ctypes.c_double, c_double_p]),
+    "pvx_welch_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                       c_double_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvx_fric_desc": (ctypes.c_int64, [c_double_p, ctypes.c_int64, ctypes.c_int, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "pvx_fric_desc_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_double_p] + [ctypes.c_void_p] * 4),
+    "pvx_fricative": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                       c_double_p, ctypes.c_double, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p]),
+    "pvx_fricative_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           c_double_p, ctypes.c_double, c_double_p] + [ctypes.c_void_p] * 6),
+    "pvx_fric_last_kernels": (ctypes.c_char_p, []),
 }
 
 

@@ -2452,6 +2452,160 @@ extern "C" int64_t pvx_xspec(const void* x, const void* y, int x_dtype, int64_t 
     return nblk;
 }
 
+// ---- fricative descriptors of many snippets of one signal (k_fric.hip) ---------------------------
+static thread_local const char* t_fric_kernels = "";
+extern "C" const char* pvx_fric_last_kernels(void) { return t_fric_kernels; }
+
+// what: 1 the spectra, 2 the descriptors and the RMS
+static int fric_args(int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, double sr, const double* freq,
+                     const double* psd, const double* desc, const int32_t* imax, const int32_t* status, const double* rms, int what) {
+    if (nrows < 0) { pvx_set_error("pvx_fricative: nrows %lld", (long long)nrows); return PVX_ERR_SIZE; }
+    if (L < 2) { pvx_set_error("pvx_fricative: snippets of %d samples (at least 2 are needed)", L); return PVX_ERR_SIZE; }
+    if (n < 0 || nwind < 2 || !(sr > 0.0)) { pvx_set_error("bad pvx_fricative argument"); return PVX_ERR_INVALID; }
+    if (x_dtype != PVX_F32 && x_dtype != PVX_F64 && x_dtype != PVX_I16) { pvx_set_error("bad x_dtype %d", x_dtype); return PVX_ERR_INVALID; }
+    if (nrows > 0) {
+        if (!starts) { pvx_set_error("null pvx_fricative starts"); return PVX_ERR_INVALID; }
+        for (int64_t r = 0; r < nrows; r++)
+            if (starts[r] < 0 || starts[r] > n - L) {
+                pvx_set_error("pvx_fricative: row %lld (samples %lld .. %lld) does not lie inside the %lld samples of the signal", (long long)r,
+                              (long long)starts[r], (long long)starts[r] + L - 1, (long long)n);
+                return PVX_ERR_SIZE;
+            }
+        if ((__int128)nrows * (std::min(nwind, L) / 2 + 1) > ((__int128)1 << 56)) { pvx_set_error("pvx_fricative: too many rows"); return PVX_ERR_INVALID; }
+        if (((what & 2) && (!freq || !desc || !imax || !status || !rms)) || (!(what & 2) && !psd)) {
+            pvx_set_error("null pvx_fricative output");
+            return PVX_ERR_INVALID;
+        }
+    }
+    return PVX_OK;
+}
+
+static int64_t fric_dev(const void* d_x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, const double* win,
+                        double sr, const double* freq, double* d_psd, double* d_desc, int32_t* d_imax, int32_t* d_status, double* d_rms,
+                        void* stream, int what) {
+    int rc;
+    if ((rc = fric_args(x_dtype, n, starts, nrows, L, nwind, sr, freq, d_psd, d_desc, d_imax, d_status, d_rms, what)) != PVX_OK) return rc;
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    t_fric_kernels = "";
+    if (nrows == 0) return 0;
+    if (!d_x) { pvx_set_error("null pvx_fricative signal"); return PVX_ERR_INVALID; }
+    if ((rc = pvx_fric_run(d_x, x_dtype, starts, nrows, L, nwind, win, sr, freq, d_psd, (what & 2) ? d_desc : nullptr, d_imax, d_status, d_rms,
+                           (hipStream_t)stream, &t_fric_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nrows;
+}
+
+static int64_t fric_host(const void* x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, const double* win,
+                         double sr, const double* freq, double* psd, double* desc, int32_t* imax, int32_t* status, double* rms, int what) {
+    int rc;
+    if ((rc = fric_args(x_dtype, n, starts, nrows, L, nwind, sr, freq, psd, desc, imax, status, rms, what)) != PVX_OK) return rc;
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    t_fric_kernels = "";
+    if (nrows == 0) return 0;
+    if (!x) { pvx_set_error("null pvx_fricative signal"); return PVX_ERR_INVALID; }
+    // a group is consecutive rows of the call with the span of samples they cover: a row's bits are those of the unchunked call
+    size_t limit = (size_t)2 << 30;
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
+    const size_t es = dtype_size(x_dtype);
+    const int64_t nhalf = std::min(nwind, L) / 2 + 1;
+    const int64_t room = std::max<int64_t>((int64_t)(limit / es), L);  // samples of a group's span
+    const int64_t maxrows = std::max<int64_t>(1, (int64_t)(limit / ((size_t)nhalf * 8)));
+    const bool tail = (what & 2) != 0;
+    DevMem dx, dpsd, ddesc, dim, dst, drms;
+    std::vector<int64_t> rel;
+    for (int64_t r0 = 0; r0 < nrows;) {
+        int64_t lo = starts[r0], hi = starts[r0] + L, r1 = r0 + 1;
+        while (r1 < nrows && r1 - r0 < maxrows) {
+            const int64_t nlo = std::min(lo, starts[r1]), nhi = std::max(hi, starts[r1] + L);
+            if (nhi - nlo > room) break;
+            lo = nlo; hi = nhi; r1++;
+        }
+        const int64_t cnt = r1 - r0;
+        rel.resize((size_t)cnt);
+        for (int64_t i = 0; i < cnt; i++) rel[(size_t)i] = starts[r0 + i] - lo;
+        if ((rc = dx.grow((size_t)(hi - lo) * es, Sizing::exact)) != PVX_OK) return rc;
+        if (psd && (rc = dpsd.grow((size_t)(cnt * nhalf) * 8, Sizing::exact)) != PVX_OK) return rc;
+        if (tail && ((rc = ddesc.grow((size_t)cnt * 56, Sizing::exact)) != PVX_OK || (rc = dim.grow((size_t)cnt * 4, Sizing::exact)) != PVX_OK ||
+                     (rc = dst.grow((size_t)cnt * 4, Sizing::exact)) != PVX_OK || (rc = drms.grow((size_t)cnt * 8, Sizing::exact)) != PVX_OK)) return rc;
+        if ((rc = host_to_device(dx.get(), (const char*)x + (size_t)lo * es, (size_t)(hi - lo) * es)) != PVX_OK) return rc;
+        if ((rc = pvx_fric_run(dx.get(), x_dtype, rel.data(), cnt, L, nwind, win, sr, freq, psd ? dpsd.as<double>() : nullptr,
+                               tail ? ddesc.as<double>() : nullptr, dim.as<int32_t>(), dst.as<int32_t>(), drms.as<double>(), nullptr,
+                               &t_fric_kernels)) != PVX_OK) return rc;
+        if (psd && (rc = device_to_host((char*)psd + (size_t)(r0 * nhalf) * 8, dpsd.get(), (size_t)(cnt * nhalf) * 8)) != PVX_OK) return rc;
+        if (tail && ((rc = device_to_host((char*)desc + (size_t)r0 * 56, ddesc.get(), (size_t)cnt * 56)) != PVX_OK ||
+                     (rc = device_to_host((char*)imax + (size_t)r0 * 4, dim.get(), (size_t)cnt * 4)) != PVX_OK ||
+                     (rc = device_to_host((char*)status + (size_t)r0 * 4, dst.get(), (size_t)cnt * 4)) != PVX_OK ||
+                     (rc = device_to_host((char*)rms + (size_t)r0 * 8, drms.get(), (size_t)cnt * 8)) != PVX_OK)) return rc;
+        r0 = r1;
+    }
+    return nrows;
+}
+
+extern "C" int64_t pvx_welch(const void* x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind, const double* win,
+                             double sr, double* psd) {
+    return fric_host(x, x_dtype, n, starts, nrows, L, nwind, win, sr, nullptr, psd, nullptr, nullptr, nullptr, nullptr, 1);
+}
+extern "C" int64_t pvx_welch_dev(const void* d_x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind,
+                                 const double* win, double sr, double* d_psd, void* stream) {
+    return fric_dev(d_x, x_dtype, n, starts, nrows, L, nwind, win, sr, nullptr, d_psd, nullptr, nullptr, nullptr, nullptr, stream, 1);
+}
+extern "C" int64_t pvx_fricative(const void* x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind,
+                                 const double* win, double sr, const double* freq, double* psd, double* desc, int32_t* imax, int32_t* status,
+                                 double* rms) {
+    return fric_host(x, x_dtype, n, starts, nrows, L, nwind, win, sr, freq, psd, desc, imax, status, rms, 3);
+}
+extern "C" int64_t pvx_fricative_dev(const void* d_x, int x_dtype, int64_t n, const int64_t* starts, int64_t nrows, int L, int nwind,
+                                     const double* win, double sr, const double* freq, double* d_psd, double* d_desc, int32_t* d_imax,
+                                     int32_t* d_status, double* d_rms, void* stream) {
+    return fric_dev(d_x, x_dtype, n, starts, nrows, L, nwind, win, sr, freq, d_psd, d_desc, d_imax, d_status, d_rms, stream, 3);
+}
+
+static int fric_desc_args(int64_t nrows, int nb, const double* psd, const double* freq, const double* desc, const int32_t* imax,
+                          const int32_t* status) {
+    if (nrows < 0 || nb < 2) { pvx_set_error("pvx_fric_desc: %lld rows of %d bins (at least 2 are needed)", (long long)nrows, nb); return PVX_ERR_SIZE; }
+    if (nrows > 0 && (!psd || !freq || !desc || !imax || !status)) { pvx_set_error("null pvx_fric_desc argument"); return PVX_ERR_INVALID; }
+    if ((__int128)nrows * nb > ((__int128)1 << 56)) { pvx_set_error("pvx_fric_desc: too many rows"); return PVX_ERR_INVALID; }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_fric_desc_dev(const double* d_psd, int64_t nrows, int nb, const double* freq, double* d_desc, int32_t* d_imax,
+                                     int32_t* d_status, void* stream) {
+    int rc;
+    if ((rc = fric_desc_args(nrows, nb, d_psd, freq, d_desc, d_imax, d_status)) != PVX_OK) return rc;
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    t_fric_kernels = "";
+    if (nrows == 0) return 0;
+    // (a row of nb bins is the half spectrum of segments of 2 (nb - 1) samples: the geometry the run derives its bin count from)
+    const int nper = 2 * (nb - 1);
+    if ((rc = pvx_fric_run(nullptr, PVX_F64, nullptr, nrows, nper, nper, nullptr, 1.0, freq, (double*)d_psd, d_desc, d_imax, d_status, nullptr,
+                           (hipStream_t)stream, &t_fric_kernels)) != PVX_OK) return rc;
+    return nrows;
+}
+
+extern "C" int64_t pvx_fric_desc(const double* psd, int64_t nrows, int nb, const double* freq, double* desc, int32_t* imax, int32_t* status) {
+    int rc;
+    if ((rc = fric_desc_args(nrows, nb, psd, freq, desc, imax, status)) != PVX_OK) return rc;
+    if ((rc = pvx_require_device()) != PVX_OK) return rc;
+    t_fric_kernels = "";
+    if (nrows == 0) return 0;
+    size_t limit = (size_t)2 << 30;
+    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
+    const int64_t rc_rows = std::min<int64_t>(nrows, std::max<int64_t>(1, (int64_t)(limit / ((size_t)nb * 8))));
+    DevMem dpsd, ddesc, dim, dst;
+    if ((rc = dpsd.alloc((size_t)(rc_rows * nb) * 8)) != PVX_OK || (rc = ddesc.alloc((size_t)rc_rows * 56)) != PVX_OK ||
+        (rc = dim.alloc((size_t)rc_rows * 4)) != PVX_OK || (rc = dst.alloc((size_t)rc_rows * 4)) != PVX_OK) return rc;
+    const int nper = 2 * (nb - 1);
+    for (int64_t r0 = 0; r0 < nrows; r0 += rc_rows) {
+        const int64_t cnt = std::min(rc_rows, nrows - r0);
+        if ((rc = host_to_device(dpsd.get(), (const char*)psd + (size_t)(r0 * nb) * 8, (size_t)(cnt * nb) * 8)) != PVX_OK) return rc;
+        if ((rc = pvx_fric_run(nullptr, PVX_F64, nullptr, cnt, nper, nper, nullptr, 1.0, freq, dpsd.as<double>(), ddesc.as<double>(),
+                               dim.as<int32_t>(), dst.as<int32_t>(), nullptr, nullptr, &t_fric_kernels)) != PVX_OK) return rc;
+        if ((rc = device_to_host((char*)desc + (size_t)r0 * 56, ddesc.get(), (size_t)cnt * 56)) != PVX_OK ||
+            (rc = device_to_host((char*)imax + (size_t)r0 * 4, dim.get(), (size_t)cnt * 4)) != PVX_OK ||
+            (rc = device_to_host((char*)status + (size_t)r0 * 4, dst.get(), (size_t)cnt * 4)) != PVX_OK) return rc;
+    }
+    return nrows;
+}
+
 // ---- full cross-correlations and their peaks block by block (k_xcorr.hip) -----------------------
 static thread_local const char* t_xcorr_kernels = "";
 extern "C" const char* pvx_xcorr_last_kernels(void) { return t_xcorr_kernels; }

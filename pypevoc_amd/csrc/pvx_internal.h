@@ -350,6 +350,15 @@ int pvx_specdesc_run(const void* d_x, int x_dtype, int64_t nfr, const double* h_
 int pvx_xspec_run(const void* d_x, const void* d_y, int x_dtype, const double* h_wind, int nwind, int step, int64_t delta, int64_t nblk,
                   int nseg, double* d_sxy, double* d_sxx, double* d_syy, hipStream_t s, const char** kernels);
 
+// fricative descriptors (k_fric.hip; include/pvx.h: pvx_fricative): nrows snippets d_x[h_starts[r] : + L] of the device signal d_x.
+// d_x non-null: the Welch spectra into d_psd [nrows][nper/2 + 1] (nper = min(nwind, L); h_win [nper] nullable: the periodic Hann
+// window; d_psd nullable when d_desc is given).  d_desc non-null: the descriptors of the psd rows into d_desc [nrows][7], d_imax,
+// d_status (h_freq [nper/2 + 1] a host array) and, with d_x, the snippets' RMS into d_rms.  d_x null: the descriptors of the rows
+// of d_psd alone.  Synchronises the stream.
+int pvx_fric_run(const void* d_x, int x_dtype, const int64_t* h_starts, int64_t nrows, int L, int nwind, const double* h_win, double sr,
+                 const double* h_freq, double* d_psd, double* d_desc, int32_t* d_imax, int32_t* d_status, double* d_rms, hipStream_t s,
+                 const char** kernels);
+
 // full cross-correlations and their peaks, block by block (k_xcorr.hip; include/pvx.h: pvx_xcorr_peak): nblk blocks of the device
 // signals d_a (la samples a block) and d_v (lv), which point at the first block's first sample.  The windows are host arrays
 // (nullable: ones), the outputs device memory (d_corr [nblk][la + lv - 1], nullable).  Synchronises the stream.

@@ -5,7 +5,9 @@ lpc2form_full and Formants(full=True)), the speech segmenter (`segmenter`: Speec
 refine_transition_points and the batched transition_points_rows; SEGMENT.md), the pitch-jump detector (`jumps`:
 JumpDetector, zscore_wind, linreg_err, linreg2_err, the batched jumps_rows and segment_and_detect_jumps; JUMPS.md) and
 the silence detector it segments with (`chunker`: SilenceDetector with the percentile discriminator, imported from that
-module and not exported here).  SyllableSegmenter and MultiChannelSegmenter are not mirrored."""
+module and not exported here) and the fricative descriptors (`fricatives`: FricativeDataFromSnip, the batched welch_rows,
+fricative_desc_rows and fricative_rows, and fricative_intervals; FRICATIVES.md).  SyllableSegmenter and
+MultiChannelSegmenter are not mirrored."""
 from . import SpeechAnalysis  # noqa: F401
 from . import glottal  # noqa: F401
 from . import formants  # noqa: F401
@@ -13,6 +15,7 @@ from . import envelope  # noqa: F401
 from . import segmenter  # noqa: F401
 from . import jumps  # noqa: F401
 from . import chunker  # noqa: F401
+from . import fricatives  # noqa: F401
 from .segmenter import SpeechSegmenter, peaks, refine_transition_points, transition_points_rows  # noqa: F401
 from .jumps import JumpDetector  # noqa: F401
 
