@@ -436,6 +436,34 @@ int64_t pvx_periodicity_dev(const double* d_x, int64_t nsamp, const double* wind
                             double* d_cand_period, double* d_cand_strength, int32_t* d_ncands,
                             int32_t* d_preferred, void* stream);
 
+/* ---- YIN f0 tracking: SoundUtils.f0yin / aubio_f0yin (pypevoc/SoundUtils.py:234-261) --------
+ *
+ * The reference's entry calls the aubio package; this is the algorithm YIN.md specifies (de Cheveigne & Kawahara,
+ * steps 1-5), not a bit-for-bit mirror of aubio.  For each frame xs = x[starts[i] : starts[i] + nwind] (starts: host
+ * array, any order, repeats allowed; every frame must lie inside the nsamp samples, else PVX_ERR_INVALID), L = nwind / 2:
+ *   d[t]  = sum_{j < L} (xs[j] - xs[j + t])^2, t = 1 .. hi + 1;  S[t] = d[1] + .. + d[t];  d'[t] = d[t] t / S[t]
+ *           (the literal 1.0 where S[t] == 0; d'[0] = 1);
+ *   pick  = the smallest t in [lo, hi] with d'[t] < tol and d'[t] < d'[t + 1]; without one (flag bit PVX_YIN_FALLBACK)
+ *           the first arg-min of d' over [lo, hi];
+ *   tau   = pick + 0.5 (s0 - s2) / (s0 - 2 s1 + s2) with s = d'[pick - 1 .. pick + 1] (pick where that denominator is 0),
+ *   freq  = sr / tau, conf = 1 - d'[pick];
+ *   a frame with S[hi + 1] == 0 (silent or constant) returns freq = conf = tau = 0, pick = 0 and flag = PVX_YIN_SILENT.
+ * 2 <= lo <= hi <= L - 2 and nwind >= 8, else PVX_ERR_INVALID; nwind > PVX_YIN_MAX_NWIND: PVX_ERR_UNSUPPORTED and no
+ * launch.  tau, flag and pick are nullable.  float64 throughout, every sum in an order fixed by (nwind, hi): a frame's
+ * result does not depend on the other frames of the call.  pvx_yin_dev: x and the outputs are device memory (starts stays
+ * a host array), work on `stream`, synchronised before the return.  Both return nfr or a negative status; nfr = 0
+ * launches nothing.  pvx_yin_last_kernels: what the calling thread's last call ran ("k_yin", "k_yin/seg2", "k_yin/seg4":
+ * the sums over j split into that many segments; "" when it had no frame).
+ */
+#define PVX_YIN_MAX_NWIND 8192
+#define PVX_YIN_FALLBACK 1
+#define PVX_YIN_SILENT 2
+int64_t pvx_yin(const double* x, int64_t nsamp, const int64_t* starts, int64_t nfr, int nwind, int lo, int hi, double tol, double sr,
+                double* freq, double* conf, double* tau, int32_t* flag, int32_t* pick);
+int64_t pvx_yin_dev(const double* d_x, int64_t nsamp, const int64_t* starts, int64_t nfr, int nwind, int lo, int hi, double tol,
+                    double sr, double* d_freq, double* d_conf, double* d_tau, int32_t* d_flag, int32_t* d_pick, void* stream);
+const char* pvx_yin_last_kernels(void);
+
 /* ---- FFT filter banks: FilterBank.specout, MelFilterBank.mfcc (pypevoc/FFTFilters.py:274-292, 352-374) ----
  *
  * pvx_filterbank: frames start at i*hop while i*hop < n - nwind (:280; n <= nwind: no frame).  Per frame

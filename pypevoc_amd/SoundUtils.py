@@ -5,7 +5,8 @@ reference.  FuncWind (:42-69) runs on the device for the named reducers np.sum /
 np.var (k_funcwind); an arbitrary Python callable has no device form and raises TypeError.
 SpecCentWind (:142-160) and SpecFlux (:196-231) run in k_specdesc.hip (pvx_specdesc, include/pvx.h; SPECDESC.md): the host
 folds the reference's bin ranges of the full spectrum onto weights per half-spectrum bin, everything per frame is on the
-device.  AvgWind (:163-193) is FuncWind's sum.  No CPU fallback."""
+device.  AvgWind (:163-193) is FuncWind's sum.  aubio_f0yin (:234-261) runs YIN in k_yin.hip (pvx_yin; YIN.md) without the
+aubio package; f0yin and f0yin_rows are its wider forms.  No CPU fallback."""
 import ctypes
 
 import numpy as np
@@ -225,3 +226,136 @@ def AvgWind(x, sr=1, nwind=1024, nhop=512, windfunc=np.blackman):
     length nwind, and in steps of nhop: sum(xw)/sum(wind)
     '''
     return FuncWind(np.sum, x, sr=sr, nwind=nwind, nhop=nhop, power=1, windfunc=windfunc)
+
+
+# ---- YIN f0 tracking (k_yin.hip) ------------------------------------------------------------------------------------
+YIN_FALLBACK, YIN_SILENT = 1, 2                                       # PVX_YIN_* of include/pvx.h
+YIN_MAX_NWIND = 8192                                                  # PVX_YIN_MAX_NWIND
+YIN_DEFAULT_TOLERANCE = 0.15
+
+
+def yin_lags(nwind, sr, fmin=None, fmax=None):
+    """The lag range [lo, hi] f0yin searches (YIN.md, step 3): lo = 2, raised to floor(sr / fmax); hi = nwind//2 - 2, lowered
+    to ceil(sr / fmin).  ValueError for nwind < 8 and for an empty range."""
+    nwind = int(nwind)
+    if nwind < 8:
+        raise ValueError("f0yin needs a window of at least 8 samples (got %d)" % nwind)
+    L = nwind // 2
+    lo, hi = 2, L - 2
+    if fmin is not None:
+        if not fmin > 0:
+            raise ValueError("fmin must be positive (got %r)" % (fmin,))
+        hi = min(int(np.ceil(sr / float(fmin))), L - 2)
+    if fmax is not None:
+        if not fmax > 0:
+            raise ValueError("fmax must be positive (got %r)" % (fmax,))
+        lo = max(2, int(np.floor(sr / float(fmax))))
+    if lo > hi:
+        raise ValueError("no lag to search: fmax %r gives lo = %d, fmin %r and nwind %d give hi = %d" % (fmax, lo, fmin, nwind, hi))
+    return lo, hi
+
+
+def yin_frames(nsamp, sr, nwind=1024, hop=512):
+    """Frame starts and times of aubio_f0yin's loop (SoundUtils.py:255, 258): starts range(0, nsamp - nwind, hop), times
+    (start + nwind/2) / sr."""
+    if int(hop) < 1:
+        raise ValueError("hop must be at least 1 (got %r)" % (hop,))
+    starts = np.arange(0, int(nsamp) - int(nwind), int(hop), dtype=np.int64)
+    return starts, (starts + int(nwind) / 2.0) / float(sr)
+
+
+def _yin_tolerance(tolerance):
+    if tolerance is not None:
+        if tolerance > 0.0 and tolerance < 1.0:                      # SoundUtils.py:243-247
+            return float(tolerance)
+        import sys
+        sys.stderr.write('Tolerance not set: Out of bounds\n')
+    return YIN_DEFAULT_TOLERANCE
+
+
+def _yin_run(y, starts, nwind, lo, hi, tol, sr):
+    """One pvx_yin launch over the frames y[s : s + nwind] for s in starts; host arrays back."""
+    nwind = int(nwind)
+    starts = np.ascontiguousarray(starts, dtype=np.int64)
+    nf = len(starts)
+    dev = _lib.is_device_array(y)
+    if dev:
+        sig = _lib.DeviceSignal(y)
+        if len(sig.shape) != 1:
+            raise ValueError("a 1-D signal is expected")
+        nx = sig.shape[0]
+    else:
+        y = np.asarray(y)
+        if y.ndim != 1:
+            raise ValueError("a 1-D signal is expected")
+        nx = len(y)
+    if nf and (starts.min() < 0 or starts.max() > nx - nwind):
+        bad = starts[(starts < 0) | (starts > nx - nwind)][0]
+        raise ValueError("the frame starting at %d leaves the signal (%d samples, window %d)" % (int(bad), nx, nwind))
+    res = {"freq": np.zeros(nf), "conf": np.zeros(nf), "tau": np.zeros(nf), "flag": np.zeros(nf, dtype=np.int32),
+           "pick": np.zeros(nf, dtype=np.int32)}
+    if nf == 0:
+        return res
+    lib = _lib.load()
+    bound = _lib.init()
+    args = (starts.ctypes.data_as(_lib.c_int64_p), nf, nwind, int(lo), int(hi), float(tol), float(sr))
+    if dev:
+        import torch
+        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
+            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
+                                % (torch.cuda.current_device(), bound))
+        if sig.dtype != np.float64:                                  # float32 / int16: every value is a float64 value
+            y = torch.as_tensor(y, device=torch.device("cuda", bound)).to(torch.float64)
+            sig = _lib.DeviceSignal(y)
+        tdev = torch.device("cuda", bound)
+        dd = torch.empty((3, nf), dtype=torch.float64, device=tdev)
+        di = torch.empty((2, nf), dtype=torch.int32, device=tdev)
+        stream = torch.cuda.current_stream()
+        _lib.check(lib.pvx_yin_dev(ctypes.c_void_p(sig.ptr), nx, *args, ctypes.c_void_p(dd[0].data_ptr()), ctypes.c_void_p(dd[1].data_ptr()),
+                                   ctypes.c_void_p(dd[2].data_ptr()), ctypes.c_void_p(di[0].data_ptr()), ctypes.c_void_p(di[1].data_ptr()),
+                                   ctypes.c_void_p(stream.cuda_stream)), "pvx_yin_dev")
+        hd, hi_ = dd.cpu().numpy(), di.cpu().numpy()
+        res.update(freq=hd[0].copy(), conf=hd[1].copy(), tau=hd[2].copy(), flag=hi_[0].copy(), pick=hi_[1].copy())
+    else:
+        x = np.ascontiguousarray(y, dtype=np.float64)                # float32 / int16 widen exactly
+        _lib.check(lib.pvx_yin(_lib.dptr(x), nx, *args, _lib.dptr(res["freq"]), _lib.dptr(res["conf"]), _lib.dptr(res["tau"]),
+                               res["flag"].ctypes.data_as(_lib.c_int32_p), res["pick"].ctypes.data_as(_lib.c_int32_p)), "pvx_yin")
+    return res
+
+
+def f0yin_rows(y, starts, nwind, sr, tolerance=None, fmin=None, fmax=None):
+    """YIN on the frames y[s : s + nwind] for s in starts (any order, repeats allowed), one launch: a dict of freq, conf,
+    tau (the refined period in samples), pick (its integer lag) and flag (YIN_FALLBACK: no dip below the tolerance, the
+    arg-min was taken; YIN_SILENT: a silent or constant frame, freq = conf = 0), one entry per start.  y: a host array
+    (float64, float32, int16, ...) or a 1-D signal already on the GPU."""
+    lo, hi = yin_lags(nwind, sr, fmin, fmax)
+    return _yin_run(y, starts, nwind, lo, hi, _yin_tolerance(tolerance), sr)
+
+
+def f0yin(y, sr, nwind=1024, hop=512, tolerance=None, fmin=None, fmax=None, full=False):
+    """f0 by YIN (YIN.md) over the frames of aubio_f0yin's loop: (freq, time, conf), one entry per frame; full=True: a
+    dict that adds tau, pick, flag and starts.  tolerance: the threshold of the first-dip rule (None or outside (0, 1):
+    0.15); fmin / fmax bound the lags searched."""
+    lo, hi = yin_lags(nwind, sr, fmin, fmax)
+    nsamp = int(_lib.DeviceSignal(y).shape[0]) if _lib.is_device_array(y) else len(y)
+    starts, time = yin_frames(nsamp, sr, nwind, hop)
+    res = _yin_run(y, starts, nwind, lo, hi, _yin_tolerance(tolerance), sr)
+    if full:
+        res.update(time=time, starts=starts)
+        return res
+    return res["freq"], time, res["conf"]
+
+
+def aubio_f0yin(y, sr, nwind=1024, hop=512, method='yin', tolerance=None):
+    ''' Applies f0 detection to a numpy vector: the reference's entry (SoundUtils.py:234-261) without the aubio package;
+    method 'yin' runs f0yin, aubio's other methods are not mirrored
+    '''
+    if method != 'yin':
+        raise NotImplementedError("aubio_f0yin: method %r is not mirrored by pypevoc_amd, only 'yin' (INTEGRATION.md)" % (method,))
+    return f0yin(y, sr, nwind=nwind, hop=hop, tolerance=tolerance)
+
+
+def yin_last_kernels():
+    """The kernel the calling thread's last f0yin / f0yin_rows launch ran: 'k_yin', 'k_yin/seg2' or 'k_yin/seg4' (a call without a
+    frame launches nothing and leaves this as it was)."""
+    return _lib.load().pvx_yin_last_kernels().decode()

@@ -139,6 +139,11 @@ SIGNATURES = {
     "pvx_periodicity_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int, c_int64_p, ctypes.c_int64,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                              ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 5),
+    "pvx_yin": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                 ctypes.c_double, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "pvx_yin_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 6),
+    "pvx_yin_last_kernels": (ctypes.c_char_p, []),
     "pvx_filterbank": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                         ctypes.c_int, ctypes.c_int, c_double_p, c_double_p]),
     "pvx_filterbank_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,

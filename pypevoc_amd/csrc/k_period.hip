@@ -22,6 +22,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "pvx_block.h"
 #include "pvx_internal.h"
 #include "pvx_mem.h"
 
@@ -31,66 +32,9 @@ constexpr int kThreads = 256;
 constexpr int kR = 4;              // lags per thread per pass
 constexpr int kLdsMax = 6144;      // windows up to 48 KB of float64 stay in LDS
 
-// ---- block reductions (fixed order: results do not depend on which workgroup runs a frame) ----------
-struct Red {
-    double d[kThreads / 64];
-    int i[kThreads / 64];
-};
-
-__device__ double block_sum(double v, Red& r) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) r.d[w] = v;
-    __syncthreads();
-    return (r.d[0] + r.d[1]) + (r.d[2] + r.d[3]);
-}
-// max ignoring NaN (fmax); -inf when every value is NaN / absent
-__device__ double block_fmax(double v, Red& r) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) r.d[w] = v;
-    __syncthreads();
-    return fmax(fmax(r.d[0], r.d[1]), fmax(r.d[2], r.d[3]));
-}
-// numpy's np.min: NaN as soon as one value is NaN
-__device__ double block_nanmin(double v, Red& r) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const double u = __shfl_xor(v, o);
-        v = (v != v || u != u) ? NAN : (u < v ? u : v);
-    }
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) r.d[w] = v;
-    __syncthreads();
-    double m = r.d[0];
-    for (int k = 1; k < kThreads / 64; k++) { const double u = r.d[k]; m = (m != m || u != u) ? NAN : (u < m ? u : m); }
-    return m;
-}
-__device__ int block_imin(int v, Red& r) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) r.i[w] = v;
-    __syncthreads();
-    return min(min(r.i[0], r.i[1]), min(r.i[2], r.i[3]));
-}
-// (score desc, index asc): the first arg-max of the reference's repeated pkmskamp.argmax()
-__device__ __forceinline__ bool better(double s, int k, double s2, int k2) { return s > s2 || (s == s2 && k < k2); }
-__device__ void block_argmax(double& s, int& k, Red& r) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const double s2 = __shfl_xor(s, o);
-        const int k2 = __shfl_xor(k, o);
-        if (better(s2, k2, s, k)) { s = s2; k = k2; }
-    }
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { r.d[w] = s; r.i[w] = k; }
-    __syncthreads();
-    s = r.d[0]; k = r.i[0];
-    for (int q = 1; q < kThreads / 64; q++) if (better(r.d[q], r.i[q], s, k)) { s = r.d[q]; k = r.i[q]; }
-}
+// block reductions in a fixed order (results do not depend on which workgroup runs a frame): pvx_block.h
+using namespace pvxb;
+static_assert(kThreads == kBlock, "the block reductions are written for 256 threads");
 
 // PeakFinder(y, minval=..., npeaks=np).findpos() (PeakFinder.py:155-194) on y[0..m): pkmskamp[k] = y[k] - miny at
 // interior maxima y[k-1] < y[k] >= y[k+1], 0 elsewhere; rounds take the best (score, index) below the previous pick

@@ -2244,6 +2244,67 @@ extern "C" int64_t pvx_periodicity(const double* x, int64_t nsamp, const double*
     return nidx;
 }
 
+// ---- YIN f0 tracking (k_yin.hip) --------------------------------------------------------------
+static thread_local const char* t_yin_kernels = "";
+extern "C" const char* pvx_yin_last_kernels(void) { return t_yin_kernels; }
+
+static int yin_args(int64_t nsamp, const int64_t* starts, int64_t nfr, int nwind, int lo, int hi, double tol, double sr) {
+    if (nsamp < 0 || nfr < 0 || (nfr > 0 && !starts)) { pvx_set_error("bad pvx_yin argument"); return PVX_ERR_INVALID; }
+    if (nwind < 8) { pvx_set_error("pvx_yin: window of %d samples (at least 8 are needed)", nwind); return PVX_ERR_INVALID; }
+    if (nwind > PVX_YIN_MAX_NWIND) { pvx_set_error("pvx_yin: window of %d samples (the kernel takes up to %d)", nwind, PVX_YIN_MAX_NWIND); return PVX_ERR_UNSUPPORTED; }
+    if (lo < 2 || lo > hi || hi > nwind / 2 - 2) {
+        pvx_set_error("pvx_yin: lags %d .. %d are not inside 2 .. nwind/2 - 2 = %d", lo, hi, nwind / 2 - 2);
+        return PVX_ERR_INVALID;
+    }
+    if (!(tol == tol) || !(sr > 0.0)) { pvx_set_error("pvx_yin: tolerance %g, sample rate %g", tol, sr); return PVX_ERR_INVALID; }
+    for (int64_t i = 0; i < nfr; i++) {
+        if (starts[i] < 0 || starts[i] > nsamp - nwind) {
+            pvx_set_error("pvx_yin: frame %lld (samples %lld .. %lld) does not lie inside the %lld samples of the signal", (long long)i,
+                          (long long)starts[i], (long long)starts[i] + nwind, (long long)nsamp);
+            return PVX_ERR_INVALID;
+        }
+    }
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_yin_dev(const double* d_x, int64_t nsamp, const int64_t* starts, int64_t nfr, int nwind, int lo, int hi, double tol,
+                               double sr, double* d_freq, double* d_conf, double* d_tau, int32_t* d_flag, int32_t* d_pick, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = yin_args(nsamp, starts, nfr, nwind, lo, hi, tol, sr)) != PVX_OK) return rc;
+    t_yin_kernels = "";
+    if (nfr == 0) return 0;
+    if (!d_x || !d_freq || !d_conf) { pvx_set_error("null pvx_yin array"); return PVX_ERR_INVALID; }
+    YinParams p = {};
+    p.x = d_x; p.nsamp = nsamp; p.nfr = nfr;
+    p.nwind = nwind; p.lo = lo; p.hi = hi; p.tol = tol; p.sr = sr;
+    p.freq = d_freq; p.conf = d_conf; p.tau = d_tau; p.flag = d_flag; p.pick = d_pick;
+    if ((rc = pvx_yin_run(p, starts, (hipStream_t)stream, &t_yin_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nfr;
+}
+
+extern "C" int64_t pvx_yin(const double* x, int64_t nsamp, const int64_t* starts, int64_t nfr, int nwind, int lo, int hi, double tol, double sr,
+                           double* freq, double* conf, double* tau, int32_t* flag, int32_t* pick) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = yin_args(nsamp, starts, nfr, nwind, lo, hi, tol, sr)) != PVX_OK) return rc;
+    t_yin_kernels = "";
+    if (nfr == 0) return 0;
+    if (!x || !freq || !conf) { pvx_set_error("null pvx_yin array"); return PVX_ERR_INVALID; }
+    const size_t db = (size_t)nfr * 8, ib = (size_t)nfr * 4;
+    DevMem dx, df, dc, dt, dg, dk;
+    if ((rc = dx.alloc((size_t)nsamp * 8)) != PVX_OK || (rc = df.alloc(db)) != PVX_OK || (rc = dc.alloc(db)) != PVX_OK ||
+        (tau && (rc = dt.alloc(db)) != PVX_OK) || (flag && (rc = dg.alloc(ib)) != PVX_OK) || (pick && (rc = dk.alloc(ib)) != PVX_OK)) return rc;
+    if ((rc = host_to_device(dx.get(), x, (size_t)nsamp * 8)) != PVX_OK) return rc;
+    const int64_t r = pvx_yin_dev(dx.as<const double>(), nsamp, starts, nfr, nwind, lo, hi, tol, sr, df.as<double>(), dc.as<double>(),
+                                  tau ? dt.as<double>() : nullptr, flag ? dg.as<int32_t>() : nullptr, pick ? dk.as<int32_t>() : nullptr, nullptr);
+    if (r < 0) return r;
+    if ((rc = device_to_host(freq, df.get(), db)) != PVX_OK || (rc = device_to_host(conf, dc.get(), db)) != PVX_OK ||
+        (tau && (rc = device_to_host(tau, dt.get(), db)) != PVX_OK) || (flag && (rc = device_to_host(flag, dg.get(), ib)) != PVX_OK) ||
+        (pick && (rc = device_to_host(pick, dk.get(), ib)) != PVX_OK)) return rc;
+    return nfr;
+}
+
 // ---- FFT filter banks (k_fbank.hip) -----------------------------------------------------------
 static thread_local const char* t_fbank_kernels = "";
 extern "C" const char* pvx_filterbank_last_kernels(void) { return t_fbank_kernels; }

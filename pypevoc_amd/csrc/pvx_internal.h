@@ -331,6 +331,25 @@ struct PeriodParams {
 // workspace the calls share, one at a time)
 int pvx_period_run(PeriodParams p, const double* h_wind, const int64_t* h_idx, hipStream_t s);
 
+// YIN f0 tracking (k_yin.hip; include/pvx.h: pvx_yin; YIN.md): the frames x[starts[i] : starts[i] + nwind], lags 1 .. hi + 1.
+struct YinParams {
+    const double* x;            // [nsamp] device
+    int64_t nsamp;
+    const int64_t* starts;      // [nfr] frame starts, device (filled in by pvx_yin_run)
+    int64_t nfr;
+    int nwind, lo, hi;
+    double tol, sr;
+    double* freq;               // [nfr] device
+    double* conf;
+    double* tau;                // nullable
+    int32_t* flag;              // nullable
+    int32_t* pick;              // nullable
+    int nblk = 0, nseg = 0, seglen = 0;   // the split of a frame's work (filled in by pvx_yin_run from nwind and hi alone)
+};
+// p.x and the outputs are device memory, h_starts a host array (the entry point checked every frame against nsamp).
+// Synchronises the stream; *kernels names what ran.
+int pvx_yin_run(YinParams p, const int64_t* h_starts, hipStream_t s, const char** kernels);
+
 // FFT filter banks (k_fbank.hip, FFTFilters.py:274-292, 352-374): band energies and cepstra of frames 0 .. nfr of the device
 // signal d_x (frame i starts at i * hop).  The window, fb [nband][nwind] (full spectrum) are host arrays; d_spec / d_cep device
 // memory (either may be null).  Synchronises the stream; *kernels names what ran.
