@@ -464,6 +464,48 @@ int64_t pvx_yin_dev(const double* d_x, int64_t nsamp, const int64_t* starts, int
                     double sr, double* d_freq, double* d_conf, double* d_tau, int32_t* d_flag, int32_t* d_pick, void* stream);
 const char* pvx_yin_last_kernels(void);
 
+/* ---- Period marks: period_marks_corr / period_marks_peak (pypevoc/Periodicity.py:573-618, 621-709) ------------
+ * One walk per row x[row_start[r] : row_stop[r]] (0 <= start <= stop <= nsamp), as MARKS.md states the two walks; times are
+ * row times (0 at the row's first sample) and the shared track (tf, f), ntf strictly increasing knots, is read at
+ * toff[r] + t (toff null: 0).  Outputs: marks (and vals) padded [nrows][max_marks], count[nrows], status[nrows].
+ * status is 0 for a walk that ended by its own loop test, else the OR of:
+ *   PVX_MARKS_NO_PEAK     a step's correlation has no local maximum            PVX_MARKS_PAST_END    s + P + W > L after P grew
+ *   PVX_MARKS_BAD_F0      f0 <= 0, P < 1, P >= 2^31, t0 < 0, no finite f0      PVX_MARKS_NO_ADVANCE  a NaN-f0 step without a positive delay_t
+ *   PVX_MARKS_CAPACITY    max_marks reached                                    PVX_MARKS_STEPS       max_steps reached
+ *   PVX_MARKS_SHORT_FIT   (peak) a returned mark had fewer than 3 fit points and is its sample
+ * and the row keeps the marks found so far.  pvx_marks_corr: row r starts at mark t0[r]; f_fallback is f0 where interp(t0)
+ * is NaN (the reference's nanmean(f)); window >= 2.  The stretch of a step lives in LDS: with Pmax = int(sr / the smallest
+ * positive finite value among f and f_fallback), 3 * window + Pmax > PVX_MARKS_CORR_MAX_LDS is PVX_ERR_UNSUPPORTED and
+ * launches nothing.  pvx_marks_peak: tf null: nf == 1 (one f0) or nf == nsamp (f per sample of x); 3 <= fit_points <=
+ * PVX_MARKS_MAX_FIT_POINTS; count excludes the walk's last mark, as the reference drops it.  The _dev variants take x and
+ * the outputs as device memory (the lists stay host memory) and run on `stream`, synchronised on return.  A row's result
+ * does not depend on the other rows of the call.  Return nrows, or a negative pvx_status.
+ * pvx_marks_last_kernels: what the calling thread's last call ran ("k_marks_corr", "k_marks_peak"; "": nothing). */
+#define PVX_MARKS_NO_PEAK 1
+#define PVX_MARKS_PAST_END 2
+#define PVX_MARKS_BAD_F0 4
+#define PVX_MARKS_NO_ADVANCE 8
+#define PVX_MARKS_CAPACITY 16
+#define PVX_MARKS_STEPS 32
+#define PVX_MARKS_SHORT_FIT 64
+#define PVX_MARKS_CORR_MAX_LDS 8000
+#define PVX_MARKS_MAX_FIT_POINTS 64
+int64_t pvx_marks_corr(const double* x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* t0,
+                       const double* toff, int64_t nrows, const double* tf, const double* f, int64_t ntf, double f_fallback, double sr,
+                       int window, double min_per, int64_t max_marks, int64_t max_steps, double* marks, int32_t* count, int32_t* status);
+int64_t pvx_marks_corr_dev(const double* d_x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* t0,
+                           const double* toff, int64_t nrows, const double* tf, const double* f, int64_t ntf, double f_fallback,
+                           double sr, int window, double min_per, int64_t max_marks, int64_t max_steps, double* d_marks,
+                           int32_t* d_count, int32_t* d_status, void* stream);
+int64_t pvx_marks_peak(const double* x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* toff,
+                       int64_t nrows, const double* tf, const double* f, int64_t ntf, int64_t nf, double sr, int fit_points,
+                       int64_t max_marks, int64_t max_steps, double* marks, double* vals, int32_t* count, int32_t* status);
+int64_t pvx_marks_peak_dev(const double* d_x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* toff,
+                           int64_t nrows, const double* tf, const double* f, int64_t ntf, int64_t nf, double sr, int fit_points,
+                           int64_t max_marks, int64_t max_steps, double* d_marks, double* d_vals, int32_t* d_count,
+                           int32_t* d_status, void* stream);
+const char* pvx_marks_last_kernels(void);
+
 /* ---- FFT filter banks: FilterBank.specout, MelFilterBank.mfcc (pypevoc/FFTFilters.py:274-292, 352-374) ----
  *
  * pvx_filterbank: frames start at i*hop while i*hop < n - nwind (:280; n <= nwind: no frame).  Per frame

@@ -274,11 +274,11 @@ class PeriodTimeSeries(PeriodSeries):
     pass
 
 
-def _unsupported_fn(name, where):
+def _unsupported_fn(name, where, see=""):
     def fn(*args, **kwargs):
         raise NotImplementedError(
             "%s (Periodicity.py:%s) is a sequential scalar walk, one decision per period, and is not mirrored by "
-            "pypevoc_amd; use the reference for it (see INTEGRATION.md, 'not mirrored')" % (name, where))
+            "pypevoc_amd; use the reference for it (see INTEGRATION.md, 'not mirrored')%s" % (name, where, see))
     fn.__name__ = name
     fn.__doc__ = "Not mirrored: Periodicity.py:%s." % where
     return fn
@@ -286,8 +286,8 @@ def _unsupported_fn(name, where):
 
 amdf = _unsupported_fn("amdf", "38-52")
 period_marks_amdf = _unsupported_fn("period_marks_amdf", "525-570")
-period_marks_corr = _unsupported_fn("period_marks_corr", "573-618")
-period_marks_peak = _unsupported_fn("period_marks_peak", "621-709")
+period_marks_corr = _unsupported_fn("period_marks_corr", "573-618", "; pypevoc_amd.marks.period_marks_corr runs it on the GPU (MARKS.md)")
+period_marks_peak = _unsupported_fn("period_marks_peak", "621-709", "; pypevoc_amd.marks.period_marks_peak runs it on the GPU (MARKS.md)")
 
 
 class PeriodByPeriod(PeriodSeries):

@@ -144,6 +144,19 @@ SIGNATURES = {
     "pvx_yin_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 6),
     "pvx_yin_last_kernels": (ctypes.c_char_p, []),
+    "pvx_marks_corr": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_int64_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64, c_double_p,
+                                        c_double_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_int64, ctypes.c_int64, c_double_p, c_int32_p, c_int32_p]),
+    "pvx_marks_corr_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p, c_double_p, c_double_p, ctypes.c_int64,
+                                            c_double_p, c_double_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                            ctypes.c_double, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    "pvx_marks_peak": (ctypes.c_int64, [c_double_p, ctypes.c_int64, c_int64_p, c_int64_p, c_double_p, ctypes.c_int64, c_double_p, c_double_p,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                        c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    "pvx_marks_peak_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p, c_double_p, ctypes.c_int64, c_double_p,
+                                            c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_int64,
+                                            ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    "pvx_marks_last_kernels": (ctypes.c_char_p, []),
     "pvx_filterbank": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,
                                         ctypes.c_int, ctypes.c_int, c_double_p, c_double_p]),
     "pvx_filterbank_dev": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p,

@@ -2305,6 +2305,160 @@ extern "C" int64_t pvx_yin(const double* x, int64_t nsamp, const int64_t* starts
     return nfr;
 }
 
+// ---- Period marks (k_marks.hip) ----------------------------------------------------------------
+static thread_local const char* t_marks_kernels = "";
+extern "C" const char* pvx_marks_last_kernels(void) { return t_marks_kernels; }
+
+static int marks_args(const char* who, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, int64_t nrows, double sr,
+                      int64_t max_marks, int64_t max_steps) {
+    if (nsamp < 0 || nrows < 0 || (nrows > 0 && (!row_start || !row_stop))) { pvx_set_error("bad %s argument", who); return PVX_ERR_INVALID; }
+    if (!(sr > 0.0) || !(sr < INFINITY)) { pvx_set_error("%s: sample rate %g", who, sr); return PVX_ERR_INVALID; }
+    if (max_marks < 1 || max_marks > INT32_MAX || max_steps < 0) {
+        pvx_set_error("%s: max_marks %lld, max_steps %lld", who, (long long)max_marks, (long long)max_steps);
+        return PVX_ERR_INVALID;
+    }
+    for (int64_t i = 0; i < nrows; i++) {
+        if (row_start[i] < 0 || row_start[i] > row_stop[i] || row_stop[i] > nsamp) {
+            pvx_set_error("%s: row %lld (samples %lld .. %lld) does not lie inside the %lld samples of the signal", who, (long long)i,
+                          (long long)row_start[i], (long long)row_stop[i], (long long)nsamp);
+            return PVX_ERR_INVALID;
+        }
+    }
+    return PVX_OK;
+}
+static int marks_track(const char* who, const double* tf, const double* f, int64_t ntf) {
+    if (!tf || !f || ntf < 1 || ntf > INT32_MAX) { pvx_set_error("%s: a track of %lld knots", who, (long long)ntf); return PVX_ERR_INVALID; }
+    for (int64_t i = 0; i < ntf; i++) {
+        if (!(tf[i] - tf[i] == 0.0) || (i > 0 && !(tf[i] > tf[i - 1]))) {
+            pvx_set_error("%s: tf must be finite and strictly increasing (knot %lld)", who, (long long)i);
+            return PVX_ERR_INVALID;
+        }
+    }
+    return PVX_OK;
+}
+
+// the LDS plan of the corr walk: *cap doubles for a step's stretch, from the largest period the track can give
+static int marks_corr_plan(const double* f, int64_t ntf, double f_fallback, double sr, int window, int* cap) {
+    double fmin = INFINITY;
+    for (int64_t i = 0; i <= ntf; i++) {
+        const double v = i < ntf ? f[i] : f_fallback;
+        if (v > 0.0 && v < fmin) fmin = v;
+    }
+    const double q = fmin < INFINITY ? sr / fmin : 0.0;
+    if (window > PVX_MARKS_CORR_MAX_LDS || !(3.0 * window + floor(q) <= (double)PVX_MARKS_CORR_MAX_LDS)) {
+        pvx_set_error("pvx_marks_corr: window %d with periods of up to %.0f samples (3 * window + period may be %d at most)", window,
+                      floor(q), PVX_MARKS_CORR_MAX_LDS);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    *cap = (window + (int)q + 2 + 1) / 2 * 2;                         // one more than Pmax: interp may round below the smallest knot
+    return PVX_OK;
+}
+
+extern "C" int64_t pvx_marks_corr_dev(const double* d_x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* t0,
+                                      const double* toff, int64_t nrows, const double* tf, const double* f, int64_t ntf, double f_fallback,
+                                      double sr, int window, double min_per, int64_t max_marks, int64_t max_steps, double* d_marks,
+                                      int32_t* d_count, int32_t* d_status, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = marks_args("pvx_marks_corr", nsamp, row_start, row_stop, nrows, sr, max_marks, max_steps)) != PVX_OK) return rc;
+    if ((rc = marks_track("pvx_marks_corr", tf, f, ntf)) != PVX_OK) return rc;
+    if (window < 2 || !(min_per == min_per) || (nrows > 0 && !t0)) { pvx_set_error("pvx_marks_corr: window %d, min_per %g", window, min_per); return PVX_ERR_INVALID; }
+    int cap = 0;
+    if ((rc = marks_corr_plan(f, ntf, f_fallback, sr, window, &cap)) != PVX_OK) return rc;
+    t_marks_kernels = "";
+    if (nrows == 0) return 0;
+    if (!d_x || !d_marks || !d_count || !d_status) { pvx_set_error("null pvx_marks_corr array"); return PVX_ERR_INVALID; }
+    MarksCorrParams p = {};
+    p.x = d_x; p.nsamp = nsamp; p.nrows = nrows; p.f_fallback = f_fallback; p.sr = sr; p.min_per = min_per;
+    p.W = window; p.cap = cap; p.max_marks = (int)max_marks; p.max_steps = max_steps;
+    p.marks = d_marks; p.count = d_count; p.status = d_status;
+    MarksRows h = {row_start, row_stop, t0, toff, tf, f, ntf, ntf};
+    if ((rc = pvx_marks_corr_run(p, h, (hipStream_t)stream, &t_marks_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nrows;
+}
+
+extern "C" int64_t pvx_marks_corr(const double* x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* t0,
+                                  const double* toff, int64_t nrows, const double* tf, const double* f, int64_t ntf, double f_fallback,
+                                  double sr, int window, double min_per, int64_t max_marks, int64_t max_steps, double* marks,
+                                  int32_t* count, int32_t* status) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = marks_args("pvx_marks_corr", nsamp, row_start, row_stop, nrows, sr, max_marks, max_steps)) != PVX_OK) return rc;
+    t_marks_kernels = "";
+    if (nrows == 0) return 0;
+    if (!x || !marks || !count || !status) { pvx_set_error("null pvx_marks_corr array"); return PVX_ERR_INVALID; }
+    const size_t mb = (size_t)nrows * (size_t)max_marks * 8, ib = (size_t)nrows * 4;
+    DevMem dx, dm, dc, ds;
+    if ((rc = dx.alloc((size_t)nsamp * 8)) != PVX_OK || (rc = dm.alloc(mb)) != PVX_OK || (rc = dc.alloc(ib)) != PVX_OK ||
+        (rc = ds.alloc(ib)) != PVX_OK) return rc;
+    if ((rc = host_to_device(dx.get(), x, (size_t)nsamp * 8)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemsetAsync(dm.get(), 0, mb, nullptr));          // the padding behind a row's marks reads as 0
+    const int64_t r = pvx_marks_corr_dev(dx.as<const double>(), nsamp, row_start, row_stop, t0, toff, nrows, tf, f, ntf, f_fallback, sr,
+                                         window, min_per, max_marks, max_steps, dm.as<double>(), dc.as<int32_t>(), ds.as<int32_t>(), nullptr);
+    if (r < 0) return r;
+    if ((rc = device_to_host(marks, dm.get(), mb)) != PVX_OK || (rc = device_to_host(count, dc.get(), ib)) != PVX_OK ||
+        (rc = device_to_host(status, ds.get(), ib)) != PVX_OK) return rc;
+    return nrows;
+}
+
+extern "C" int64_t pvx_marks_peak_dev(const double* d_x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* toff,
+                                      int64_t nrows, const double* tf, const double* f, int64_t ntf, int64_t nf, double sr, int fit_points,
+                                      int64_t max_marks, int64_t max_steps, double* d_marks, double* d_vals, int32_t* d_count,
+                                      int32_t* d_status, void* stream) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = marks_args("pvx_marks_peak", nsamp, row_start, row_stop, nrows, sr, max_marks, max_steps)) != PVX_OK) return rc;
+    if (tf) {
+        if ((rc = marks_track("pvx_marks_peak", tf, f, ntf)) != PVX_OK) return rc;
+        nf = ntf;
+    } else {
+        ntf = 0;
+        if (!f || (nf != 1 && nf != nsamp)) {
+            pvx_set_error("pvx_marks_peak: without tf, f holds one value or one per sample (%lld values, %lld samples)", (long long)nf, (long long)nsamp);
+            return PVX_ERR_INVALID;
+        }
+    }
+    if (fit_points < 3) { pvx_set_error("pvx_marks_peak: fit_points %d (at least 3)", fit_points); return PVX_ERR_INVALID; }
+    if (fit_points > PVX_MARKS_MAX_FIT_POINTS) {
+        pvx_set_error("pvx_marks_peak: fit_points %d (the kernel takes up to %d)", fit_points, PVX_MARKS_MAX_FIT_POINTS);
+        return PVX_ERR_UNSUPPORTED;
+    }
+    t_marks_kernels = "";
+    if (nrows == 0) return 0;
+    if (!d_x || !d_marks || !d_vals || !d_count || !d_status) { pvx_set_error("null pvx_marks_peak array"); return PVX_ERR_INVALID; }
+    MarksPeakParams p = {};
+    p.x = d_x; p.nsamp = nsamp; p.nrows = nrows; p.sr = sr; p.fit_points = fit_points;
+    p.max_marks = (int)max_marks; p.max_steps = max_steps;
+    p.marks = d_marks; p.vals = d_vals; p.count = d_count; p.status = d_status;
+    MarksRows h = {row_start, row_stop, nullptr, toff, tf, f, ntf, nf};
+    if ((rc = pvx_marks_peak_run(p, h, (hipStream_t)stream, &t_marks_kernels)) != PVX_OK) return rc;   // synchronises the stream
+    return nrows;
+}
+
+extern "C" int64_t pvx_marks_peak(const double* x, int64_t nsamp, const int64_t* row_start, const int64_t* row_stop, const double* toff,
+                                  int64_t nrows, const double* tf, const double* f, int64_t ntf, int64_t nf, double sr, int fit_points,
+                                  int64_t max_marks, int64_t max_steps, double* marks, double* vals, int32_t* count, int32_t* status) {
+    int rc = pvx_require_device();
+    if (rc != PVX_OK) return rc;
+    if ((rc = marks_args("pvx_marks_peak", nsamp, row_start, row_stop, nrows, sr, max_marks, max_steps)) != PVX_OK) return rc;
+    t_marks_kernels = "";
+    if (nrows == 0) return 0;
+    if (!x || !marks || !vals || !count || !status) { pvx_set_error("null pvx_marks_peak array"); return PVX_ERR_INVALID; }
+    const size_t mb = (size_t)nrows * (size_t)max_marks * 8, ib = (size_t)nrows * 4;
+    DevMem dx, dm, dv, dc, ds;
+    if ((rc = dx.alloc((size_t)nsamp * 8)) != PVX_OK || (rc = dm.alloc(mb)) != PVX_OK || (rc = dv.alloc(mb)) != PVX_OK ||
+        (rc = dc.alloc(ib)) != PVX_OK || (rc = ds.alloc(ib)) != PVX_OK) return rc;
+    if ((rc = host_to_device(dx.get(), x, (size_t)nsamp * 8)) != PVX_OK) return rc;
+    PVX_HIP_CHECK(hipMemsetAsync(dm.get(), 0, mb, nullptr));
+    PVX_HIP_CHECK(hipMemsetAsync(dv.get(), 0, mb, nullptr));
+    const int64_t r = pvx_marks_peak_dev(dx.as<const double>(), nsamp, row_start, row_stop, toff, nrows, tf, f, ntf, nf, sr, fit_points,
+                                         max_marks, max_steps, dm.as<double>(), dv.as<double>(), dc.as<int32_t>(), ds.as<int32_t>(), nullptr);
+    if (r < 0) return r;
+    if ((rc = device_to_host(marks, dm.get(), mb)) != PVX_OK || (rc = device_to_host(vals, dv.get(), mb)) != PVX_OK ||
+        (rc = device_to_host(count, dc.get(), ib)) != PVX_OK || (rc = device_to_host(status, ds.get(), ib)) != PVX_OK) return rc;
+    return nrows;
+}
+
 // ---- FFT filter banks (k_fbank.hip) -----------------------------------------------------------
 static thread_local const char* t_fbank_kernels = "";
 extern "C" const char* pvx_filterbank_last_kernels(void) { return t_fbank_kernels; }

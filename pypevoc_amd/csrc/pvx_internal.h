@@ -350,6 +350,44 @@ struct YinParams {
 // Synchronises the stream; *kernels names what ran.
 int pvx_yin_run(YinParams p, const int64_t* h_starts, hipStream_t s, const char** kernels);
 
+// Period marks (k_marks.hip; include/pvx.h: pvx_marks_corr / pvx_marks_peak; MARKS.md): one walk per row x[row_start : row_stop].
+// The row lists and the track are device pointers the run functions fill in from the host lists of MarksRows.
+struct MarksRows {
+    const int64_t *row_start, *row_stop;   // [nrows], host
+    const double *t0, *toff;               // [nrows], host (t0: the corr walk only; toff may be null)
+    const double *tf, *f;                  // the shared track, host: ntf knots and nf values (tf null: nf == 1 or nf == nsamp)
+    int64_t ntf, nf;
+};
+struct MarksCorrParams {
+    const double* x;            // device
+    int64_t nsamp, nrows;
+    const int64_t *row_start, *row_stop;
+    const double *t0, *toff, *tf, *f;
+    int ntf;
+    double f_fallback;          // f0 where interp(t0) is NaN (the reference's nanmean(f))
+    double sr, min_per;
+    int W, cap;                 // window_size; doubles of LDS the stretch may take (>= W + the largest P)
+    int max_marks;
+    int64_t max_steps;
+    double* marks;              // [nrows][max_marks]
+    int32_t *count, *status;    // [nrows]
+};
+struct MarksPeakParams {
+    const double* x;
+    int64_t nsamp, nrows;
+    const int64_t *row_start, *row_stop;
+    const double *toff, *tf, *f;
+    int ntf, fmode;             // fmode 0: f[0] everywhere; 1: f[row_start + i]; 2: interp(toff + i / sr, tf, f)
+    double sr;
+    int fit_points, max_marks;
+    int64_t max_steps;
+    double *marks, *vals;       // [nrows][max_marks]
+    int32_t *count, *status;
+};
+// launch and synchronise the stream; *kernels names what ran
+int pvx_marks_corr_run(MarksCorrParams p, const MarksRows& h, hipStream_t s, const char** kernels);
+int pvx_marks_peak_run(MarksPeakParams p, const MarksRows& h, hipStream_t s, const char** kernels);
+
 // FFT filter banks (k_fbank.hip, FFTFilters.py:274-292, 352-374): band energies and cepstra of frames 0 .. nfr of the device
 // signal d_x (frame i starts at i * hop).  The window, fb [nband][nwind] (full spectrum) are host arrays; d_spec / d_cep device
 // memory (either may be null).  Synchronises the stream; *kernels names what ran.
