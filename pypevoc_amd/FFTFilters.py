@@ -202,11 +202,7 @@ class FilterBank(object):
                 raise ValueError("specout takes a 1-D signal")
             n = sig.shape[0]
             nfr = _lib.nframes_host(n, nwind, hop)
-            bound = _lib.init()
-            if torch.cuda.current_device() != bound:                 # the outputs and the stream must be the bound device's
-                raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                    % (torch.cuda.current_device(), bound))
-            dev = torch.device("cuda", bound)
+            dev = _lib.bound_torch_device()   # the outputs and the stream must be the bound device's
             dspec = torch.empty(max(nfr * nband, 1), dtype=torch.float64, device=dev)
             dcep = torch.empty(max(nfr * nband * cpx, 1) if cep_mode else 1, dtype=torch.float64, device=dev)
             stream = torch.cuda.current_stream()

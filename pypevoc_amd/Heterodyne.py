@@ -139,11 +139,7 @@ class HeterodyneHarmonic(object):
     def _device(self):
         """torch, its device object and current stream for the `_dev` entries (the signal lives on the bound device)"""
         import torch
-        bound = _lib.init()
-        if torch.cuda.current_device() != bound:
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        return torch, torch.device("cuda", bound), torch.cuda.current_stream()
+        return torch, _lib.bound_torch_device(), torch.cuda.current_stream()
 
     def _extract(self, fvec, wind, hop, first, count, halve_dc):
         """pvx_hetharm: harmonics first .. first+count-1 of the normalised track fvec -> (ah [nfr, count], icent [nfr])"""

@@ -144,11 +144,7 @@ class PeriodSeries(object):
                        "pvx_periodicity")
         else:
             import torch
-            bound = _lib.init()
-            if torch.cuda.current_device() != bound:                 # the outputs and the stream must be the bound device's
-                raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                    % (torch.cuda.current_device(), bound))
-            dev = torch.device("cuda", bound)
+            dev = _lib.bound_torch_device()   # the outputs and the stream must be the bound device's
             dper = torch.empty(max(nf * ncand, 1), dtype=torch.float64, device=dev)
             dst = torch.empty_like(dper)
             dcnt = torch.empty(max(nf, 1), dtype=torch.int32, device=dev)

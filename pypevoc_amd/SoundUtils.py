@@ -133,7 +133,7 @@ def specdesc_run(x, wind, hop, nfr, measure, a=None, b=None):
     anything with __cuda_array_interface__), read in place.  Raises PvxError without a GPU.  nfr <= 0: an empty array; the
     library is told (last_kernels() is '' afterwards) and launches nothing."""
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     wind = np.ascontiguousarray(wind, dtype=np.float64)
     nwind, hop, nfr = len(wind), int(hop), max(int(nfr), 0)
     nout = nwind // 2 if measure == SD_PSD else nfr
@@ -147,10 +147,7 @@ def specdesc_run(x, wind, hop, nfr, measure, a=None, b=None):
         sig = _lib.DeviceSignal(x)
         if len(sig.shape) != 1:
             raise ValueError("a 1-D signal is expected")
-        if torch.cuda.current_device() != bound:                     # the output and the stream must be the bound device's
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        dout = torch.empty(max(nout, 1), dtype=torch.float64, device=torch.device("cuda", bound))
+        dout = torch.empty(max(nout, 1), dtype=torch.float64, device=_lib.bound_torch_device())   # the output and the stream must be the bound device's
         stream = torch.cuda.current_stream()
         got = _lib.check(lib.pvx_specdesc_dev(ctypes.c_void_p(sig.ptr), sig.dtype_code, sig.shape[0], _lib.dptr(wind), nwind, hop, nfr, measure,
                                               pa, pb, ctypes.c_void_p(dout.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "pvx_specdesc_dev")
@@ -297,17 +294,14 @@ def _yin_run(y, starts, nwind, lo, hi, tol, sr):
     if nf == 0:
         return res
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     args = (starts.ctypes.data_as(_lib.c_int64_p), nf, nwind, int(lo), int(hi), float(tol), float(sr))
     if dev:
         import torch
-        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
+        tdev = _lib.bound_torch_device()                             # the outputs and the stream must be the bound device's
         if sig.dtype != np.float64:                                  # float32 / int16: every value is a float64 value
-            y = torch.as_tensor(y, device=torch.device("cuda", bound)).to(torch.float64)
+            y = torch.as_tensor(y, device=tdev).to(torch.float64)
             sig = _lib.DeviceSignal(y)
-        tdev = torch.device("cuda", bound)
         dd = torch.empty((3, nf), dtype=torch.float64, device=tdev)
         di = torch.empty((2, nf), dtype=torch.int32, device=tdev)
         stream = torch.cuda.current_stream()

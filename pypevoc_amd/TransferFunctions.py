@@ -111,7 +111,7 @@ def xspec_run(x, y, wind, step, start, delta, nblk, nseg):
     block of conj(Y) X (complex128), |X|^2 and |Y|^2; y None: (None, sxx, None).  x, y: host arrays, or both 1-D float32 /
     float64 / int16 signals of one type already on the GPU, read in place.  Raises PvxError without a GPU."""
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     wind = np.ascontiguousarray(wind, dtype=np.float64)
     nwind, step, start, delta, nblk, nseg = len(wind), int(step), int(start), int(delta), max(int(nblk), 0), int(nseg)
     nb = nwind // 2 + 1
@@ -126,11 +126,8 @@ def xspec_run(x, y, wind, step, start, delta, nblk, nseg):
             raise ValueError("1-D signals are expected")
         if two and sy.dtype_code != sx.dtype_code:
             raise TypeError("device-resident signals must share one sample type (got %s and %s)" % (sx.dtype, sy.dtype))
-        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
+        dev = _lib.bound_torch_device()                              # the outputs and the stream must be the bound device's
         n = min(sx.shape[0], sy.shape[0]) if two else sx.shape[0]
-        dev = torch.device("cuda", bound)
         dxx = torch.empty(max(nblk * nb, 1), dtype=torch.float64, device=dev)
         dyy = torch.empty(max(nblk * nb, 1), dtype=torch.float64, device=dev) if two else None
         dxy = torch.empty(max(2 * nblk * nb, 1), dtype=torch.float64, device=dev) if two else None

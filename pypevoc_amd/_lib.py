@@ -433,15 +433,22 @@ def is_device_array(x):
     return hasattr(x, "__cuda_array_interface__") and not isinstance(x, np.ndarray)
 
 
-def device_run(nbytes_out, launch):
-    """Run `launch(out_ptr, stream_ptr)` with a float64 device output block of nbytes_out/8 elements
-    on torch's current stream, return the block as a host numpy array."""
+def bound_torch_device():
+    """The torch.device the library is bound to.  The `_dev` entries get torch's current stream and tensors torch allocates:
+    raises PvxError where that is not the device torch works on."""
     import torch
     bound = init()
     if torch.cuda.current_device() != bound:
         raise PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
                        % (torch.cuda.current_device(), bound))
-    out = torch.empty(nbytes_out // 8, dtype=torch.float64, device=torch.device("cuda", bound))
+    return torch.device("cuda", bound)
+
+
+def device_run(nbytes_out, launch):
+    """Run `launch(out_ptr, stream_ptr)` with a float64 device output block of nbytes_out/8 elements
+    on torch's current stream, return the block as a host numpy array."""
+    import torch
+    out = torch.empty(nbytes_out // 8, dtype=torch.float64, device=bound_torch_device())
     stream = torch.cuda.current_stream()
     launch(out.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
     stream.synchronize()

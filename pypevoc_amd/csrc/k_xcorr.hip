@@ -26,6 +26,7 @@
 
 #include "pvx_internal.h"
 #include "pvx_mem.h"
+#include "pvx_host.h"
 
 namespace {
 
@@ -265,11 +266,7 @@ int ncus() {
     return 256;
 }
 
-size_t device_limit() {
-    size_t limit = (size_t)2 << 30;                                   // per buffer
-    if (const char* e = getenv("PVX_MAX_DEVICE_BYTES")) { const long long v = atoll(e); if (v > 0) limit = (size_t)v; }
-    return limit;
-}
+size_t device_limit() { return pvx_device_bytes_limit((size_t)2 << 30); }   // per buffer
 
 int run_locked(XcorrWs& w, XcParams p, int x_dtype, const double* h_win_a, const double* h_win_v, hipStream_t s, const char** kernels) {
     int rc;

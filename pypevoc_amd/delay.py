@@ -93,16 +93,13 @@ def xcorr_peaks(a, v, la, lv=None, start=0, delta=None, nblk=None, window_a=None
     wa, wv = _window(window_a, la, "window_a"), _window(window_v, lv, "window_v")
     nlag = la + lv - 1
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     mode = _DETREND[detrend]
     pa = None if wa is None else _lib.dptr(wa)
     pv = None if wv is None else _lib.dptr(wv)
     if on_device:
         import torch
-        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        dev = torch.device("cuda", bound)
+        dev = _lib.bound_torch_device()   # the outputs and the stream must be the bound device's
         dlag = torch.empty(max(nblk, 1), dtype=torch.int32, device=dev)
         dpeak = torch.empty(max(nblk, 1), dtype=torch.float64, device=dev)
         dcorr = torch.empty(max(nblk * nlag, 1), dtype=torch.float64, device=dev) if full else None

@@ -132,15 +132,12 @@ def _run_corr(x, starts, stops, t0, toff, sr, tf, f, window_size, min_per, max_m
     if nrows == 0:
         return marks, count, status
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     args = (n, starts.ctypes.data_as(_lib.c_int64_p), stops.ctypes.data_as(_lib.c_int64_p), _lib.dptr(t0), _opt(toff), nrows, _lib.dptr(tf),
             _lib.dptr(f), len(tf), fallback, float(sr), W, float(min_per), max_marks, max_steps)
     if sig is not None:
         import torch
-        if torch.cuda.current_device() != bound:
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        tdev = torch.device("cuda", bound)
+        tdev = _lib.bound_torch_device()
         dm = torch.zeros((nrows, max_marks), dtype=torch.float64, device=tdev)
         di = torch.empty((2, nrows), dtype=torch.int32, device=tdev)
         stream = torch.cuda.current_stream()
@@ -190,16 +187,13 @@ def _run_peak(x, starts, stops, toff, sr, tf, f, fit_points, max_marks, max_step
     if nrows == 0:
         return marks, vals, count, status
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     nf = 1 if scalar_f else len(f)
     args = (n, starts.ctypes.data_as(_lib.c_int64_p), stops.ctypes.data_as(_lib.c_int64_p), _opt(toff), nrows, _opt(tf), _lib.dptr(f),
             0 if tf is None else len(tf), nf, float(sr), fit_points, max_marks, max_steps)
     if sig is not None:
         import torch
-        if torch.cuda.current_device() != bound:
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        tdev = torch.device("cuda", bound)
+        tdev = _lib.bound_torch_device()
         dm = torch.zeros((2, nrows, max_marks), dtype=torch.float64, device=tdev)
         di = torch.empty((2, nrows), dtype=torch.int32, device=tdev)
         stream = torch.cuda.current_stream()

@@ -108,7 +108,7 @@ def _formants_run(x, preemph, down, taps, wind, hop, nfr, order, Fs, want=("nkep
     dict whose keys name rows that, for a signal on the GPU, are not copied to the host: it receives their flat device
     tensors instead (speech/envelope.py reads the lpc rows there).  For a host signal it is left as it is."""
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     ptr, code, n, keep, on_dev = glottal._signal(x)
     nfr, order, nwind = int(nfr), int(order), len(wind)
     wind = np.ascontiguousarray(wind, dtype=np.float64)
@@ -120,10 +120,7 @@ def _formants_run(x, preemph, down, taps, wind, hop, nfr, order, Fs, want=("nkep
             0 if taps is None else len(taps), _lib.dptr(wind), nwind, int(hop), nfr, order, float(Fs))
     if on_dev:
         import torch
-        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        dev = torch.device("cuda", bound)
+        dev = _lib.bound_torch_device()   # the outputs and the stream must be the bound device's
         outs = {k: torch.empty(max(int(np.prod(shapes[k])), 1), dtype=torch.int32 if k == "nkept" else torch.float64, device=dev)
                 for k in want}
         rc = lib.pvx_formants_dev(*head, *[ctypes.c_void_p(outs[k].data_ptr()) if k in outs else None for k in names],

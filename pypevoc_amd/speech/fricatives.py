@@ -70,7 +70,7 @@ def _run(x, starts, length, nwind, sr, window, want_psd, want_desc):
     """pvx_welch / pvx_fricative (or their _dev forms for a signal on the GPU): (freq, psd or None, desc, imax, status, rms)
     as host arrays, the last four None unless want_desc."""
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
     nrows, length, nwind, sr = len(starts), int(length), int(nwind), float(sr)
     if length < 2 or nwind < 2:                                      # (the library's own answer: no geometry to size the arrays by)
@@ -85,10 +85,7 @@ def _run(x, starts, length, nwind, sr, window, want_psd, want_desc):
         sx = _lib.DeviceSignal(x)
         if len(sx.shape) != 1:
             raise ValueError("a 1-D signal is expected")
-        if torch.cuda.current_device() != bound:                     # the outputs and the stream must be the bound device's
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        dev = torch.device("cuda", bound)
+        dev = _lib.bound_torch_device()   # the outputs and the stream must be the bound device's
         n = int(sx.shape[0])
         dpsd = torch.empty(max(nrows * nb, 1), dtype=torch.float64, device=dev) if want_psd else None
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -81,13 +81,11 @@ def _check(rc, what, sing):
     return _lib.check(rc, what)
 
 
-def _device_outputs(bound, shapes):
+def _device_outputs(shapes):
     """float64 device blocks (torch tensors on the bound device) of the given element counts, and torch's current stream."""
     import torch
-    if torch.cuda.current_device() != bound:                         # the outputs and the stream must be the bound device's
-        raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                            % (torch.cuda.current_device(), bound))
-    outs = [None if c is None else torch.empty(max(c, 1), dtype=torch.float64, device=torch.device("cuda", bound)) for c in shapes]
+    dev = _lib.bound_torch_device()                                  # the outputs and the stream must be the bound device's
+    outs = [None if c is None else torch.empty(max(c, 1), dtype=torch.float64, device=dev) for c in shapes]
     return outs, torch.cuda.current_stream()
 
 
@@ -95,7 +93,7 @@ def _iaif_run(x, nwind, hop, nfr, hp_b, lpc_wind, ola_wind, tract_order, glottal
     """pvx_iaif on x: (glot, dglot, g, dg, vt, gc) as host float64 arrays; glot / dglot None without `ola`, g / dg None
     without `frames`.  x: a host array, or a float32 / float64 / int16 1-D signal already on the GPU, read in place."""
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     ptr, code, n, keep, on_dev = _signal(x)
     nwind, hop, nfr, n_it = int(nwind), int(hop), max(int(nfr), 0), int(n_it)
     pt, pg = int(tract_order), int(glottal_order)
@@ -111,7 +109,7 @@ def _iaif_run(x, nwind, hop, nfr, hp_b, lpc_wind, ola_wind, tract_order, glottal
     head = (ctypes.c_void_p(ptr), code, n, nwind, hop, nfr, _lib.dptr(hp_b), len(hp_b), _lib.dptr(lpc_wind),
             _lib.dptr(ola_wind) if ola else None, pt, pg, float(leak), n_it)
     if on_dev:
-        douts, stream = _device_outputs(bound, counts)
+        douts, stream = _device_outputs(counts)
         rc = lib.pvx_iaif_dev(*head, *[None if t is None else ctypes.c_void_p(t.data_ptr()) for t in douts], ctypes.byref(sing),
                               ctypes.c_void_p(stream.cuda_stream))
         _check(rc, "pvx_iaif_dev", sing)
@@ -132,7 +130,7 @@ def lpc_frames(x, order, nwind, hop, wind=None):
     (len(x) - nwind) // hop + 1, as a host array [frames][order + 1]: one device call, a workgroup per frame.
     order <= 128, nwind <= 16384.  A frame whose autocorrelation is singular (silence) raises np.linalg.LinAlgError."""
     lib = _lib.load()
-    bound = _lib.init()
+    _lib.init()
     ptr, code, n, keep, on_dev = _signal(x)
     order, nwind, hop = int(order), int(nwind), int(hop)
     if order > nwind:
@@ -145,7 +143,7 @@ def lpc_frames(x, order, nwind, hop, wind=None):
     nfr = (n - nwind) // hop + 1 if n >= nwind and nwind > 0 else 0
     sing = ctypes.c_int64(-1)
     if on_dev:
-        (dout,), stream = _device_outputs(bound, [nfr * (order + 1)])
+        (dout,), stream = _device_outputs([nfr * (order + 1)])
         rc = lib.pvx_lpc_dev(ctypes.c_void_p(ptr), code, n, pw, nwind, hop, nfr, order, ctypes.c_void_p(dout.data_ptr()), ctypes.byref(sing),
                              ctypes.c_void_p(stream.cuda_stream))
         _check(rc, "pvx_lpc_dev", sing)

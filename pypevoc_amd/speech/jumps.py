@@ -302,11 +302,7 @@ def jumps_rows(t, f0, mag, lengths=None, pitch_t_hop=0.02, regressor_t=0.5, t_th
     _check_sides("jumps_rows", WIN_LINREG2, wle, wle)
     if nsl < 1:
         raise ValueError("jumps_rows: slope_t is shorter than one pitch hop")
-    bound = _lib.init()
-    dev = torch.device("cuda", bound)
-    if torch.cuda.current_device() != bound:
-        raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                            % (torch.cuda.current_device(), bound))
+    dev = _lib.bound_torch_device()
 
     def on_device(a, dtype):
         if isinstance(a, torch.Tensor):

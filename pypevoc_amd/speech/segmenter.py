@@ -137,11 +137,7 @@ class _DeviceBank(object):
             raise NotImplementedError("a filter bank of %d bands: the kernels take up to %d (PVX_FBANK_MAX_NBAND)" % (self.nband, ff.MAX_NBAND))
         if self.nband < 1:
             raise ValueError("a filter bank without bands")
-        bound = _lib.init()
-        if torch.cuda.current_device() != bound:
-            raise _lib.PvxError("torch's current device is cuda:%d but libpvx_hip is bound to device %d (pypevoc_amd._lib.init(device))"
-                                % (torch.cuda.current_device(), bound))
-        self.device = torch.device("cuda", bound)
+        self.device = _lib.bound_torch_device()
         if _lib.is_device_array(w):
             sig = _lib.DeviceSignal(w)
         else:
